@@ -8,6 +8,10 @@ Weights: seeded synthetic yolov7 weights (no checkpoints offline), packed once o
 RCCL-broadcast.  N > 1 is launched by torch.distributed.run, one process per GPU; per-GPU work is
 fixed (weak scaling); value = all images processed / max-over-ranks wall time of the K timed steps.
 
+A plain run sets up, warms up, times the K steps, writes the last step's outputs if --dump-outputs DIR
+is given, and prints the headline fields (value, ms_per_step, config ...).  Everything below needs runs
+of its own after the timed region and is reported only with --full.
+
 roofline: per kernel instantiation (the kernels the dispatch picks, yv7_op_kernels): launches, mean
 serial launch time (HIP event pairs on each op's own dispatches, two forwards after the timed region,
 every kernel alone on the chip — the durations a rocprofv3 kernel trace of a serial forward reports),
@@ -75,6 +79,13 @@ def parse(argv=None):
     ap.add_argument('--inputs', type=int, default=4, help='distinct resident input batches the steps rotate '
                     'through (4 x 78.6 MB fp16 at bs32 640: more than the 256 MiB Infinity Cache holds)')
     ap.add_argument('--map-frames', type=int, default=16, help='frames of the mAP@0.5 parity sample')
+    ap.add_argument('--full', action='store_true', help='after the timed steps also run everything beside the '
+                    'headline: the serial per-kernel roofline forwards, detect.py\'s forward / NMS split, the NMS '
+                    'load figures, the all-gather timing, the CPU baseline and the mAP@0.5 parity sample (`roofline`, '
+                    '`detail`, `parity`, `cpu_baseline`, `map50_parity` of the result line).  Without it the run '
+                    'sets up, warms up, times the steps and prints the headline fields only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='after the timed steps write what the last '
+                    'timed step computed as DIR/<name>.npy (see dump_outputs)')
     return ap.parse_args(argv)
 
 
@@ -268,6 +279,36 @@ def cpu_baseline(model_name, img, seconds, plan=None, dev=None, parity_frames=16
     if plan is not None and parity_frames > 0:
         out['map_parity'] = map_parity(net, fused, img, plan, dev, parity_frames)
     return out
+
+
+DUMP_Z_ROWS = 2048   # anchor rows of z kept per image (seeded sample)
+
+
+def dump_outputs(path, det, src, cnt, z):
+    """--dump-outputs: the last timed step's results as float .npy files, for comparing two builds
+    output for output (the inputs and weights are seeded, so equal arguments give equal inputs).
+
+      det.npy      [B, max_det, 6] float32  xyxy, conf, cls per image (what Inflight.result / nms_batched hand back)
+      src_row.npy  [B, max_det]    float64  anchor row of every kept box
+      count.npy    [B]             float32  boxes kept per image
+      z_rows.npy   [R]             float64  a seeded sample of the N anchor rows (all of them when N <= R)
+      z_sample.npy [B, R, no]      float32  the forward's decoded predictions at those rows (the NMS's input)
+
+    Entries of det / src_row past an image's count are buffer contents the NMS never wrote: stored as 0."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    det, src, cnt = det.cpu(), src.cpu(), cnt.cpu()
+    unused = torch.arange(det.shape[1])[None, :] >= cnt[:, None].long()
+    N = z.shape[1]
+    rows = min(N, DUMP_Z_ROWS, max(1, (48 << 20) // (z.shape[0] * z.shape[2] * 4)))
+    idx = torch.randperm(N, generator=torch.Generator().manual_seed(0))[:rows].sort().values
+    out = {'det': det.masked_fill(unused[..., None], 0.0).float(),
+           'src_row': src.masked_fill(unused, 0).double(),
+           'count': cnt.float(),
+           'z_rows': idx.double(),
+           'z_sample': z[:, idx.to(z.device)].float().cpu()}
+    for name, t in out.items():
+        np.save(os.path.join(path, name + '.npy'), t.contiguous().numpy())
 
 
 def main(argv=None):
@@ -481,6 +522,61 @@ def main(argv=None):
         dist.all_gather(tl, t)
         rank_elapsed = [float(v.item()) for v in tl]
         elapsed = max(rank_elapsed)
+    value = world * B * a.steps / elapsed
+    dispatch_env = {k: v for k, v in sorted(os.environ.items()) if k.startswith('YV7_')}
+
+    def headline():
+        """The result line of a plain run (and the first fields of a --full one)."""
+        return {
+            'metric': 'images/sec (640×640) + mAP@0.5 parity vs ref; 1/2/4/8 MI355X',
+            'value': round(value, 2),
+            'unit': 'images/sec',
+            'n_gpus': world,
+            'steps': a.steps,
+            'warmup': a.warmup,
+            'ms_per_step': round(elapsed / a.steps * 1e3, 3),
+            'higher_is_better': True,
+            'scaling': 'weak',
+            'vs_baseline': None,
+            'dtype': a.dtype,
+            'data': 'synthetic',
+            'config': {'workload': f'{a.model} {"P6" if plan.nl == 4 else "P5"} {H}x{W} bs={B}/GPU {a.dtype}: libyv7 forward + GPU NMS '
+                                   f'(conf 0.25, iou 0.45, max_det 300)'
+                                   + (' + RCCL all-gather of detections' if distributed else ''),
+                       'global_batch': world * B, 'img': H, 'parallelism': f'dp{world}',
+                       'rccl_world_size': dist.get_world_size() if distributed else 1,
+                       'weights': 'seeded synthetic, RCCL-broadcast' if distributed else 'seeded synthetic',
+                       'resident_input_batches': len(xin), 'dispatch_env': dispatch_env},
+        }
+
+    def emit(res):
+        if json_fd is None:
+            print(json.dumps(res), flush=True)
+        else:
+            os.write(json_fd, (json.dumps(res) + '\n').encode())
+
+    def finish():
+        if distributed:
+            beat('final barrier')
+            dist.barrier()
+            wd.stop()
+            dist.destroy_process_group()
+
+    if a.dump_outputs and rank == 0 and a.steps + a.warmup > 0:
+        # the last step's buffers: untouched since the timed region (the --full diagnostics below write z /
+        # det / src / cnt of slot 0 on the plain paths, so the dump comes first)
+        if runner is not None:
+            last = runner.n - 1
+            dump_outputs(a.dump_outputs, *runner.result(last), runner.z[last % nstreams])
+        else:
+            k = (nstep[0] - 1) % nbuf
+            dump_outputs(a.dump_outputs, dets[k], srcs[k], cnts[k], zs[k])
+    if not a.full:
+        # the timed region above is the same with and without --full (the per-op events of its first
+        # forwards included: `value` means what it always did); a plain run stops here
+        if rank == 0:
+            emit(headline())
+        return finish()
 
     from yv7 import _lib as L
     from yv7.runtime import kernel_key
@@ -621,30 +717,10 @@ def main(argv=None):
                 and cfg.get('dtype', 'f16') == a.dtype and dom['kernel'] in tj.get('kernels', {}):
             traffic = round(tj['kernels'][dom['kernel']]['hbm_bytes_per_launch'])
             traffic_src = f'profiles/{os.path.basename(PMC_TRAFFIC)} ({tj.get("tree", "")})'
-    dispatch_env = {k: v for k, v in sorted(os.environ.items()) if k.startswith('YV7_')}
 
     if rank == 0:
-        value = world * B * a.steps / elapsed
-        res = {
-            'metric': 'images/sec (640×640) + mAP@0.5 parity vs ref; 1/2/4/8 MI355X',
-            'value': round(value, 2),
-            'unit': 'images/sec',
-            'n_gpus': world,
-            'steps': a.steps,
-            'warmup': a.warmup,
-            'ms_per_step': round(elapsed / a.steps * 1e3, 3),
-            'higher_is_better': True,
-            'scaling': 'weak',
-            'vs_baseline': None,
-            'dtype': a.dtype,
-            'data': 'synthetic',
-            'config': {'workload': f'{a.model} {"P6" if plan.nl == 4 else "P5"} {H}x{W} bs={B}/GPU {a.dtype}: libyv7 forward + GPU NMS '
-                                   f'(conf 0.25, iou 0.45, max_det 300)'
-                                   + (' + RCCL all-gather of detections' if distributed else ''),
-                       'global_batch': world * B, 'img': H, 'parallelism': f'dp{world}',
-                       'rccl_world_size': dist.get_world_size() if distributed else 1,
-                       'weights': 'seeded synthetic, RCCL-broadcast' if distributed else 'seeded synthetic',
-                       'resident_input_batches': len(xin), 'dispatch_env': dispatch_env},
+        res = headline()
+        res.update({
             'roofline': {'bound': dom['bound'], 'achieved': round(ach, 1), 'peak': peak, 'unit': unit,
                          'frac': round(ach / peak, 4), 'traffic': traffic,
                          'traffic_unit': 'HBM bytes per launch of this kernel (PMC: 2 x FETCH_SIZE + WRITE_SIZE, '
@@ -682,7 +758,7 @@ def main(argv=None):
                        'mean_dets_per_image': round(count_mean, 1), 'rows_per_image': N, 'nms_load': nms_load,
                        'nms_overlapped_with_next_forward': pipeline or nstreams > 1, 'hip_graph': graph is not None,
                        'sub_batches': nsplit, 'streams': nstreams, 'h2d_uint8_frames': bool(a.h2d)},
-        }
+        })
         # the parity bars behind `map50_parity` (tests/), stated with the line
         res['parity'] = {
             'fp32_plan_vs_oracle': 'every z element within 1e-4 * scale + |ref32 - ref64| (DEVIATION from '
@@ -704,15 +780,8 @@ def main(argv=None):
                                                parity_frames=a.map_frames)
             if 'map_parity' in res['cpu_baseline']:
                 res['map50_parity'] = res['cpu_baseline']['map_parity']['map50']
-        if json_fd is None:
-            print(json.dumps(res), flush=True)
-        else:
-            os.write(json_fd, (json.dumps(res) + '\n').encode())
-    if distributed:
-        beat('final barrier')
-        dist.barrier()
-        wd.stop()
-        dist.destroy_process_group()
+        emit(res)
+    finish()
 
 
 def run_rank(argv=None):

@@ -9,7 +9,7 @@ cd $R && mkdir -p $O
 export PYTHONPATH=$R/yolo-series_amd:$R
 run() {   # name, args...
   local n=$1; shift
-  timeout -k 10 300 python -u bench.py --steps 40 --warmup 5 --no-cpu-baseline "$@" > $O/$n.json 2> $O/$n.err || { tail $O/$n.err; exit 1; }
+  timeout -k 10 300 python -u bench.py --steps 40 --warmup 5 --full --no-cpu-baseline "$@" > $O/$n.json 2> $O/$n.err || { tail $O/$n.err; exit 1; }
   python -c "import json;d=json.load(open('$O/$n.json'));print('$n', d['value'], d['unit'], d['config'].get('workload'))"
 }
 run f16 && run w6 --model yolov7-w6 --img 1280 --batch 8 && run fp8 --dtype fp8 && run tiny --model yolov7-tiny && run f16b

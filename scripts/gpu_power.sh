@@ -8,7 +8,7 @@ O=gpurun_out/$TAG
 cd $R && mkdir -p $O
 export PYTHONPATH=$R/yolo-series_amd:$R
 timeout -k 5 20 rocm-smi --showpower --showclocks --showtemp > $O/idle.txt 2>&1
-timeout -k 10 300 python -u bench.py --steps 1500 --warmup 20 --no-cpu-baseline $EXTRA > $O/bench.json 2> $O/bench.err &
+timeout -k 10 300 python -u bench.py --steps 1500 --warmup 20 --full --no-cpu-baseline $EXTRA > $O/bench.json 2> $O/bench.err &
 BP=$!
 for i in $(seq 1 60); do
   kill -0 $BP 2>/dev/null || break

@@ -16,8 +16,8 @@ for c in FETCH_SIZE WRITE_SIZE; do
 done
 cd $R && python3 scripts/pmc_traffic_kernels.py $O/pmc_FETCH_SIZE $O/pmc_WRITE_SIZE $O/pmc_traffic.json "$TREE" || exit 1
 cp $O/pmc_traffic.json profiles/${TAG}_pmc_traffic.json
-timeout -k 10 400 python -u bench.py > $O/bench.json 2> $O/bench.err || exit $?
+timeout -k 10 400 python -u bench.py --full > $O/bench.json 2> $O/bench.err || exit $?
 cat $O/bench.json
 cd /tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/bench_kt -o kt -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline > $R/$O/bench_kt.json 2> $R/$O/bench_kt.err || exit 1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/bench_kt -o kt -- python3 $R/bench.py --steps 20 --warmup 5 --full --no-cpu-baseline > $R/$O/bench_kt.json 2> $R/$O/bench_kt.err || exit 1
 cd $R && python3 scripts/roofline_check.py $O/serial_kt $O/bench.json $O/serial_ops.json > $O/roofline_check.txt; cat $O/roofline_check.txt

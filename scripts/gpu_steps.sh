@@ -62,7 +62,7 @@ for step in "$@"; do
     bench)
       for r in $(seq 1 ${arg:-2}); do
         f=$O/bench_${n}_$r.json
-        env $(envof "$envs") timeout -k 10 300 python -u bench.py  --steps 40 --warmup 5 --no-cpu-baseline $BENCH_ARGS \
+        env $(envof "$envs") timeout -k 10 300 python -u bench.py  --steps 40 --warmup 5 --full --no-cpu-baseline $BENCH_ARGS \
           > $f 2> ${f%.json}.err || exit 1
         python -c "import json;d=json.load(open('$f'));print('bench', '$f', '$envs', d['value'], d['detail']['serial_forward_ms'])"
       done ;;
@@ -70,7 +70,7 @@ for step in "$@"; do
       for r in $(seq 1 ${arg:-2}); do
         f=$O/benchw6_${n}_$r.json
         env $(envof "$envs") timeout -k 10 300 python -u bench.py --model yolov7-w6 --batch 8 --img 1280 --steps 40 \
-          --warmup 5 --no-cpu-baseline > $f 2> ${f%.json}.err || exit 1
+          --warmup 5 --full --no-cpu-baseline > $f 2> ${f%.json}.err || exit 1
         python -c "import json;d=json.load(open('$f'));print('benchw6', '$f', '$envs', d['value'], d['detail']['serial_forward_ms'])"
       done ;;
     dispatch)

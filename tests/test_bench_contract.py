@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_bench_json_line():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '6', '--warmup', '2',
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '6', '--warmup', '2', '--full',
                         '--no-cpu-baseline'], capture_output=True, text=True, timeout=240, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -41,3 +41,41 @@ def test_bench_json_line():
     assert d['config']['resident_input_batches'] >= 4 and isinstance(d['config']['dispatch_env'], dict)
     load = d['detail']['nms_load']
     assert load['conf_0.25']['candidates_per_image'] >= load['conf_0.5']['candidates_per_image'] > 0
+
+
+HEADLINE = ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling',
+            'vs_baseline', 'dtype', 'data', 'config')
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_and_dump(tmp_path):
+    """A plain run (no --full) prints the headline fields only, and --dump-outputs writes the last timed
+    step's results as float .npy files: detections consistent with their counts and with conf 0.25."""
+    import numpy as np
+    out = tmp_path / 'dump'
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '4', '--warmup', '2',
+                        '--dump-outputs', str(out)], capture_output=True, text=True, timeout=240, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert tuple(d) == HEADLINE
+    assert d['unit'] == 'images/sec' and d['higher_is_better'] is True and d['dtype'] == 'f16' and d['steps'] == 4
+    assert abs(d['value'] - 32 * 1000.0 / d['ms_per_step']) / d['value'] < 0.02
+    arrs = {f[:-4]: np.load(out / f) for f in sorted(os.listdir(out))}
+    assert sorted(arrs) == ['count', 'det', 'src_row', 'z_rows', 'z_sample']
+    assert all(v.dtype in (np.float32, np.float64) for v in arrs.values())
+    assert sum(v.nbytes for v in arrs.values()) <= 64 << 20
+    det, src, cnt, rows, z = (arrs[k] for k in ('det', 'src_row', 'count', 'z_rows', 'z_sample'))
+    assert det.shape == (32, 300, 6) and src.shape == (32, 300) and cnt.shape == (32,)
+    assert z.shape == (32, len(rows), 85) and np.all(np.diff(rows) > 0) and np.isfinite(z).all()
+    assert cnt.sum() > 0
+    for b in range(32):
+        n = int(cnt[b])
+        assert 0 <= n <= 300 and not det[b, n:].any() and not src[b, n:].any()
+        assert np.all(det[b, :n, 4] > 0.25) and np.all(np.diff(det[b, :n, 4]) <= 0)   # kept boxes, best first
+        assert np.all((0 <= src[b, :n]) & (src[b, :n] < 25200))
+        # a kept box whose anchor row is in the z sample: its score is that row's obj * cls
+        for j in np.nonzero(np.isin(src[b, :n], rows))[0]:
+            zr = z[b, np.searchsorted(rows, src[b, j])]
+            assert det[b, j, 4] == np.float32(zr[4] * zr[5 + int(det[b, j, 5])])
