@@ -155,7 +155,8 @@ int yv7_op_kernels(yv7_plan* plan, int B, int H, int W, int x_dtype, char* buf, 
 
 /* Force the kernel configuration of one CONV / DETECT op (0 = the tuned dispatch, the default).  For
  * parity tests of every kernel variant and A/B timing; the accepted values are the real kernel
- * configurations of the fp16 dispatch (csrc/conv_f16.hip), never its microbenchmark hooks.  A split-K
+ * configurations of the fp16 dispatch (the `abi` rows of csrc/conv_f16.hip's forced-variant table),
+ * never its microbenchmark hooks.  A split-K
  * variant changes yv7_workspace_bytes. */
 int yv7_set_op_variant(yv7_plan* plan, int op, int variant);
 

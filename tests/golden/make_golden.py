@@ -8,6 +8,7 @@ regressions.  Inputs are stored with the expected outputs.
                       + for each case: det rows / kept anchor rows / counts
   tiny64.npz          yolov7-tiny, synthetic weights seed 0, frames seed 1 [1,3,64,96]: z and the
                       per-level raw logits (fp32)
+(dispatch_fp16.txt is not made here: scripts/dump_dispatch.py writes it on an MI355X, tests/test_dispatch_pin.py.)
 """
 import os
 import sys

@@ -1,6 +1,6 @@
 """Parity at the bench's own configuration: yolov7 (P5) 640x640, batch 32 — BASELINE configs[1].
 
-Kernel choice in libyv7 depends on the tile count of each layer (csrc/conv_f16.hip launch_conv_f16 /
+Kernel choice in libyv7 depends on the tile count of each layer (csrc/conv_f16.hip pick_tuned /
 choose), so the kernels behind the headline number (the persistent weight-stationary 3x3, the 256 x
 256 persistent rings on 3x3 and 1x1 layers, split-K on the 20 x 20 layers, the pooled 1x1, the fused
 stem, the Detect epilogue with row scores) run only at this batch and resolution.  Here the exact

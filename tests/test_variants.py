@@ -2,7 +2,8 @@
 (yv7_set_op_variant), checked op by op against a plain PyTorch fp32 reference of the same op on the
 op's own input (tests/opcheck.py).
 
-The tuned dispatch (csrc/conv_f16.hip launch_conv_f16 / choose) picks among these by tile count, so
+The tuned dispatch (csrc/conv_f16.hip pick_tuned / choose; the forced variants are its forced_rows table,
+the launch tables csrc/conv_f16_launch.h) picks among these by tile count, so
 a small frame exercises only some of them; forcing each one on every layer shape of yolov7 /
 yolov7-tiny covers them all: the generic tile kernels (1, 2, 8), the 8-wave LDS-DMA rings (4-7),
 the halo and weight-stationary 3x3 kernels (10, 11, and 15: its half-patch ring form), every ring configuration with 1, 2 and 4 K
@@ -15,7 +16,8 @@ low-resolution 3x3 kernel (270-273: 80 / 64-pixel tiles of 4 images x 4 columns,
 without the stagger; 302 / 303: cin 256 with 128-channel N slices) and
 the alternative Detect heads (92, 97, and 99: the 64 x 256 ring that was the default before the
 persistent head).  A variant a layer's shape
-does not support falls back to the tuned kernel, which the check then covers again.
+does not support runs the register-staged tile kernel instead (conv_f16.hip pick_forced), which the check
+then covers again.
 Reference computation: models/common.py:110-111 (Conv.fuseforward), models/yolo.py:46-57 (Detect).
 """
 import pytest

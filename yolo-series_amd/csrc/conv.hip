@@ -265,7 +265,8 @@ static bool use_v1() {
 bool det_writes_rowbest(int dtype) { return dtype == 1 && !use_v1(); }
 
 hipError_t launch_conv(int dtype, const ConvParams& p, bool detect, hipStream_t st) {
-  // fp16: the tuned kernel of conv_f16.hip (YV7_CONV_V1=1 selects this file's generic kernel, for A/B)
+  // fp16: the kernel conv_f16.hip's dispatch picks from the conv_f16_* / conv_det families
+  // (YV7_CONV_V1=1 selects this file's generic kernel, for A/B)
   const bool v1 = use_v1();
   if (p.pool) return dtype == 1 ? launch_conv_f16(p, detect, st) : hipErrorInvalidValue;   // MP-folded 1x1
   // cout <= 32 (the stem of every model, tiny's narrow layers): this kernel's BK=32 steps waste less
