@@ -1,7 +1,7 @@
 """CPU interpreter of a compiled plan (test infrastructure only, never a product path).
 
 Executes yv7.graph.compile_model()'s op list with plain torch CPU ops on NHWC fp32 tensors, reading the
-packed weight blob exactly as the HIP runtime does (csrc/runtime.cpp: tensor shapes from `shift`,
+packed weight blob exactly as the HIP runtime does (csrc/plan_layout.cpp and forward.cpp: tensor shapes from `shift`,
 channel slices by offset, weights [cout_pad32][k][k][cin_pad] with K padded to 64).  Comparing its z
 with the oracle's checks the graph compiler — concat placement, SPPCSPC pool cascade, ReOrg / stem
 fusion, sibling-conv merging, detect-row layout — on CPU, independent of the GPU kernels.

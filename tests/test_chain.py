@@ -1,4 +1,4 @@
-"""The chained low-resolution 3x3 launch (csrc/conv_lr.hip conv3x3_chain_kernel, runtime.cpp find_chain):
+"""The chained low-resolution 3x3 launch (csrc/conv_lr.hip conv3x3_chain_kernel, forward.cpp find_chain):
 an ELAN block's 3x3 stack (cfg/deploy/yolov7.yaml:65-68, 84-87, 98-101, 113-116, 128-131 — Conv.fuseforward,
 models/common.py:110-111, four times in a row) as ONE launch whose layers hand rows to each other through
 per-band ready counters.  Measured slower than the per-layer launches (profiles/r6_chain/), so it is

@@ -127,7 +127,7 @@ Choice choose(const ConvParams& p, int variant) {
 
 }  // namespace
 
-// The split-K queries answer from the ring rule alone (split_scratch calls them with parameters that
+// The split-K queries answer from the ring rule alone (plan_layout.cpp calls them with parameters that
 // carry no output pitch or offset).
 size_t conv_splitk_part_bytes(const ConvParams& p) {
   const Choice c = choose(p, p.variant ? p.variant : env_variant());   // (choose() keeps this under 2 GiB)

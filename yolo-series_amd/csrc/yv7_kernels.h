@@ -8,7 +8,7 @@
 
 namespace yv7 {
 
-// Live per-op kernel timing (runtime.cpp's profile mode).  While a forward is profiled the runtime
+// Live per-op kernel timing (forward.cpp's profile mode).  While a forward is profiled the runtime
 // points op_events() at the current op's (start, stop) event pair, and every kernel of the op is
 // launched through hipExtLaunchKernel with the first launch carrying `start` and each launch `stop`:
 // the pair then spans the op's own dispatches (the begin / end timestamps rocprofv3's kernel trace
@@ -23,7 +23,7 @@ inline OpEvents& op_events() {
   return e;
 }
 // Dry run (yv7_op_kernels): while `dry` is set, YV7_LAUNCH launches nothing and records the host stub
-// of the kernel the dispatch picked (runtime.cpp turns it into the symbol rocprofv3 reports).
+// of the kernel the dispatch picked (forward.cpp's yv7_op_kernels turns it into the symbol rocprofv3 reports).
 struct LaunchRec {
   bool dry = false;
   int n = 0;
@@ -252,5 +252,16 @@ bool stem_supported(int cin, int ca, int cb, int sa);
 hipError_t launch_stem(const StemParams& p, int x_dtype, hipStream_t st);
 hipError_t launch_copy(int dtype, const void* x, int B, int H, int W, int xc, int xoff, void* y, int yc, int yoff,
                        int C, hipStream_t st);
+// nms.hip / preprocess.hip
+size_t nms_workspace_bytes(int B, int N, int no, int multi, int max_nms);
+hipError_t launch_nms(const float* z, const void* rowbest, int B, int N, int no, float conf, float iou, int multi,
+                      int agnostic, int per_class, const int32_t* classes, int ncls, int max_det, int max_nms,
+                      float* det, int64_t* src_row, int32_t* count, void* ws, hipStream_t st);
+hipError_t launch_row_best(const float* z, int B, int N, int no, void* rowbest, hipStream_t st);
+size_t letterbox_workspace_bytes(int nh, int nw);
+hipError_t launch_letterbox(const uint8_t* src, int B, int H, int W, int nh, int nw, int top, int left, int oh,
+                            int ow, const uint8_t pad[3], int out_kind, void* dst, void* ws, hipStream_t st);
+hipError_t launch_end2end_pack(const float* det, const int32_t* count, int B, int max_det, int topk,
+                               int32_t* num_dets, float* boxes, float* scores, int32_t* classes, hipStream_t st);
 
 }  // namespace yv7
