@@ -94,7 +94,7 @@ RAGGED = {'nc': 3, 'depth_multiple': 1.0, 'width_multiple': 1.0,
                        [-1, 1, 'Conv', [128, 1, 1]],   # 17
                        [-1, 1, 'Conv', [96, 3, 2]]],   # 18 @32: s2, cin 128 (P5)
           'head': [[[14, 16, 18], 1, 'Detect', ['nc', 'anchors']]]}
-# register-weight 1x1 configurations (conv_w1.hip W1_CFGS) -> the input width each one takes
+# register-weight 1x1 configurations (conv_w1.hip w1_rows) -> the input width each one takes
 W1_CIN = {290: 128, 291: 256, 292: 512, 293: 256, 294: 128, 295: 512, 302: 256, 303: 256}
 
 

@@ -493,8 +493,8 @@ bool det_pring_supported(const ConvParams& p) {
          p.nrows % 4 == 0 && p.xoff % 8 == 0 && p.xc % 8 == 0 && p.H == p.Ho && p.W == p.Wo;
 }
 
-hipError_t launch_det_pring(const ConvParams& p, int cus, hipStream_t st) {
-  const long T = (p.M + 63) / 64;
+hipError_t launch_det_pring(const ConvParams& p, hipStream_t st) {
+  const long T = (p.M + 63) / 64, cus = device_cus();
   const long per = (T + cus - 1) / cus;
   const int grid = (int)((T + per - 1) / per);
   // microbenchmark hooks (scripts/detbench.hip; the ABI never accepts them): 98 = no sigmoid staging,
@@ -504,7 +504,7 @@ hipError_t launch_det_pring(const ConvParams& p, int cus, hipStream_t st) {
   // 512); 94 = the persistent head with staged weights, kept as a forced variant.  YV7_DET_RW=0: off.
   // In-network A/B, same box (profiles/r5_det/rw/, rw512/): 256->255 @80 82.7 -> 67.3 us, 512->255 @40
   // 38.9 -> 35.6 us.
-  static const int rw = [] { const char* e = getenv("YV7_DET_RW"); return e ? atoi(e) : 1; }();
+  static const int rw = env_int("YV7_DET_RW", 1);
   if (rw && (p.variant == 0 || p.variant == 91) && det_rw_supported(p)) {
     if (p.variant == 91) {   // its hook (no pixel DMA)
       if (p.kpad == 256) YV7_LAUNCH((conv_det_rw_kernel<8, 1>), dim3(grid), dim3(512), 0, st, p);
@@ -512,12 +512,12 @@ hipError_t launch_det_pring(const ConvParams& p, int cus, hipStream_t st) {
       return hipGetLastError();
     }
     // YV7_DET_RWD: pixel stages in flight (conv_det_rw_kernel's D; 0 = the round-5 two-slot schedule)
-    static const int rwd = [] { const char* e = getenv("YV7_DET_RWD"); return e ? atoi(e) : 4; }();
+    static const int rwd = env_int("YV7_DET_RWD", 4);
     // 32-pixel tiles at K = 512 (round 6): 1x1 512->255 @40 at bs 32 is 800 tiles of 64 = 4 rounds on 200
     // blocks, or 1600 of 32 = 7 half-size rounds on 229 — 33.7 -> 31.5 us in-network, same box; at K = 256
     // (256->255 @80, 3200 / 6400 tiles) the halved tiles lose, 60.6 -> 70.0 (profiles/r6_det/bm32/).
     // YV7_DET_BM=32 / 64 forces either.
-    static const int bm_env = [] { const char* e = getenv("YV7_DET_BM"); return e ? atoi(e) : 0; }();
+    static const int bm_env = env_int("YV7_DET_BM", 0);
     const int bm = bm_env ? bm_env : (p.kpad == 512 ? 32 : 64);
     if (bm == 32 && rwd == 4) {
       const long T2 = (p.M + 31) / 32, per2 = (T2 + cus - 1) / cus;
@@ -537,7 +537,7 @@ hipError_t launch_det_pring(const ConvParams& p, int cus, hipStream_t st) {
   }
   // one 64-pixel tile per CU at most (yolov7 bs 32's P5 head): the one-tile head with its deep ring (round 6;
   // YV7_DET_1T=0: off)
-  static const int one_tile = [] { const char* e = getenv("YV7_DET_1T"); return e ? atoi(e) : 1; }();
+  static const int one_tile = env_int("YV7_DET_1T", 1);
   if (one_tile && p.variant == 0 && T <= cus && det_lds(64, 256) <= 4 * (64 + 256) * ROWB) {
     YV7_LAUNCH(conv_det_1tile_kernel, dim3((unsigned)T), dim3(512), 0, st, p);
     return hipGetLastError();

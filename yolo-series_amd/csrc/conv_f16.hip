@@ -22,8 +22,6 @@
 //    the tile leaves as full 16-byte NHWC row chunks into the output's channel slice (zero-copy concat);
 //  * accumulators start at the bias; the activation is a compile-time constant in the epilogue;
 //  * XCD-aware bijective block remap: consecutive tiles (all N tiles of an M tile) share an XCD's L2.
-#include <cstdlib>
-
 #include "conv_f16_common.h"
 #include "conv_f16_launch.h"
 
@@ -44,7 +42,12 @@ namespace {
 
 // YV7_CONV_F16=<n> forces variant <n> on every op that carries no variant of its own
 int env_variant() {
-  static const int v = [] { const char* e = getenv("YV7_CONV_F16"); return e ? atoi(e) : 0; }();
+  static const int v = env_int("YV7_CONV_F16", 0);
+  return v;
+}
+// YV7_LR=0 takes conv_lr.hip out of the tuned rules: lr_default_cfg (stride 1) and pick_tuned's stride-2 rule
+int env_lr() {
+  static const int v = env_int("YV7_LR", 1);
   return v;
 }
 
@@ -59,7 +62,7 @@ struct Pick {
 
 // The dispatch's 8-phase-ring rule (pick_tuned quotes the measurements behind it).
 bool p8_default(const ConvParams& p) {
-  static const int on = [] { const char* e = getenv("YV7_P8"); return e ? atoi(e) : 1; }();
+  static const int on = env_int("YV7_P8", 1);
   const bool one = p.k == 1 && p.s == 1 && p.pad == 0;
   const long t256 = (long)((p.M + 255) / 256) * ((p.cout + 255) / 256);
   // (1x1 K = 512 -> 512 @80, 1600 tiles: 167 -> 159 us in-network, profiles/r3u_tune.txt)
@@ -105,7 +108,7 @@ Choice choose(const ConvParams& p, int variant) {
     if (p.k > 1) {
       if (t128 <= 400) c.cfg = R128x128s2;
       if (t128 <= 256 && nk >= 36) c.S = 2;
-      static const long s4max = [] { const char* e = getenv("YV7_SPLIT4_TILES"); return e ? atol(e) : 128L; }();
+      static const long s4max = env_int("YV7_SPLIT4_TILES", 128);
       // yolov7-w6 bs 8, 512->512 @20: 100 tiles x 4 K parts (72 -> 35 us); at 200 tiles (yolov7 bs 32,
       // 256->256 @20) four parts lose to two: 33 -> 46 us (YV7_SPLIT4_TILES=256 A/B)
       if (t128 <= s4max && nk >= 36) c.S = 4;
@@ -141,8 +144,7 @@ int conv_splitk_tiles(const ConvParams& p) {
 }
 
 int lr_default_cfg(const ConvParams& p) {
-  static const int lr = [] { const char* e = getenv("YV7_LR"); return e ? atoi(e) : 1; }();
-  if (lr && !p.pool && (long)p.M <= 204800 && p.k == 3 && p.s == 1 &&
+  if (env_lr() && !p.pool && (long)p.M <= 204800 && p.k == 3 && p.s == 1 &&
       !((long)p.B * (p.H / 16) * (p.W / 16) >= 800 && ws64_supported(p))) {
     const bool t5 = p.H % 5 == 0;
     const long t128 = (long)((p.B + 3) / 4) * (p.H / (t5 ? 5 : 4)) * (p.W / 4) * (p.cout / 128);
@@ -183,7 +185,7 @@ Pick pick_pool(const ConvParams& p, bool det) {
   if (p.pool != 2 || p.k != 1 || p.s != 2 || p.pad != 0 || det || p.cin % 64) return {F_INVALID};
   // in-network A/B over the five yolov7 MP+1x1 pairs (us, 128x128 / 64x128): 256->128 @160 111 / 104,
   // 512->256 @80 71 / 68, 256->256 @40 16.9 / 15.1 (1024->512 @40 folds no more: 52 vs 46.5 unfused)
-  static const int pcfg = [] { const char* e = getenv("YV7_POOL_CFG"); return e ? atoi(e) : 0; }();
+  static const int pcfg = env_int("YV7_POOL_CFG", 0);
   if (p.cout <= 64) return {F_TILE, T128x64pool};
   return {F_TILE, pcfg == 1 ? T128x128pool : T64x128pool};
 }
@@ -191,7 +193,7 @@ Pick pick_pool(const ConvParams& p, bool det) {
 Pick pick_det(const ConvParams& p, int variant) {
   // Detect head: the persistent head (conv_det_pring_kernel) where it applies; 98 = its
   // microbenchmark hook (no staging), 99 = the 64 x 256 ring below (the round-2 default)
-  static const int det_pring = [] { const char* e = getenv("YV7_DET_PRING"); return e ? atoi(e) : 1; }();
+  static const int det_pring = env_int("YV7_DET_PRING", 1);
   if (((variant == 0 && det_pring) || variant == 94 || variant == 98 || variant == 96 || variant == 95 ||
        variant == 93 || variant == 91) && det_pring_supported(p))
     return {F_DET};
@@ -317,7 +319,7 @@ Pick pick_tuned(const ConvParams& p) {
   // (cfg 6), 128->128 @80 65.6 -> 62.2 / 65.0 -> 63.0 (cfg 7), 128->256 @80 116.2 -> 108.2 (cfg 8);
   // yolov7-w6 bs 8 128->128 @160 68.4 -> 61.4, 128->256 @160 116.2 -> 106.5.  64->64 below 1 M pixels
   // and the 64-output 128-input layers (57.1 vs 38.3) keep the dispatch below.  YV7_S1=0: off.
-  static const int s1k = [] { const char* e = getenv("YV7_S1"); return e ? atoi(e) : 1; }();
+  static const int s1k = env_int("YV7_S1", 1);
   if (s1k && p.k == 3 && p.s == 1 && !p.pool && (long)p.M >= 204800) {
     int cfg = -1;
     if (p.cin == 64 && p.cout == 64 && (long)p.M >= 1000000) cfg = 6;
@@ -341,7 +343,7 @@ Pick pick_tuned(const ConvParams& p) {
   // 128->128 s2 @160 102.2 -> 74.0 (cfg 3); yolov7-w6 bs 8 128->256 s2 @320 159.2 -> 123.6 (cfg 4).  The
   // 51 200-pixel layers (128->128 s2 @80, w6 128->256 s2 @160) are equal either way and keep the
   // dispatch below.  YV7_S2=0: off.
-  static const int s2k = [] { const char* e = getenv("YV7_S2"); return e ? atoi(e) : 1; }();
+  static const int s2k = env_int("YV7_S2", 1);
   if (s2k && p.k == 3 && p.s == 2 && (long)p.M >= 204800 && (p.cin == 64 || p.cin == 128)) {
     const int cfg = p.cin == 64 ? 0 : (p.cout >= 256 ? 4 : 3);
     if (s2_supported(p, cfg)) return {F_S2, cfg};
@@ -353,7 +355,7 @@ Pick pick_tuned(const ConvParams& p) {
   // yolov7-w6 bs 8 128->128 @320 91.3 -> 73.3, 512->256 @160 90.7 -> 65.5; 256->128 with a 128-channel
   // N slice (cfg 7; profiles/r5_misc/tune_small_w6.txt) @320 139.9 -> 123.6, @160 43.7 -> 34.1.  Narrower
   // grids keep the rings below.  YV7_W1=0: off.
-  static const int w1k = [] { const char* e = getenv("YV7_W1"); return e ? atoi(e) : 1; }();
+  static const int w1k = env_int("YV7_W1", 1);
   if (w1k && one && !p.pool) {
     int cfg = -1;
     if (p.cin == 128 && p.M >= 409600) cfg = 0;
@@ -373,9 +375,7 @@ Pick pick_tuned(const ConvParams& p) {
   // (one layer forced at a time, profiles/r5_s2/tune_deep_w6.txt, us, cfg 4 -> 7: yolov7-w6 bs 8 512->768
   // s2 @80 109.1 -> 101.5, 256->384 s2 @80 37.7 -> 31.3; yolov7 bs 32 256->256 s2 @40 keeps cfg 4: 27.0
   // vs 28.8)
-  // YV7_LR=0 switches this stride-2 rule off here; the stride-1 rule above reads it inside lr_default_cfg
-  static const int lr = [] { const char* e = getenv("YV7_LR"); return e ? atoi(e) : 1; }();
-  if (lr && p.k == 3 && p.s == 2 &&
+  if (env_lr() && p.k == 3 && p.s == 2 &&
       ((long)((p.M + 127) / 128) * ((p.cout + 127) / 128) <= 256 ||
        (p.M <= 12800 && !(t2n_s2 >= 150 && t2n_s2 <= 250 && p.cout >= 512)))) {
     const int cfg = (p.M >= 12800 && p.cout >= 384 && lr_supported(p, 7)) ? 7 : 4;
@@ -385,7 +385,7 @@ Pick pick_tuned(const ConvParams& p) {
   // column-group halo ring (conv_hring.hip, variant 262).  Single-layer sweep, bs 32 640, same box
   // (profiles/r3_hring2_tune.txt, us, dispatch -> 262): 3x3 128->128 @80 80.0 / 80.4 / 82.7 / 81.0 ->
   // 67.2 / 67.9 / 69.3 / 68.4, 128->256 @80 139.1 -> 121.4.  YV7_HRING=0: off.
-  static const int hring = [] { const char* e = getenv("YV7_HRING"); return e ? atoi(e) : 1; }();
+  static const int hring = env_int("YV7_HRING", 1);
   if (hring && hring_supported(p) && p.cout % 128 == 0 &&
       (long)p.B * (p.Ho / 16) * (p.Wo / 16) * (p.cout / 128) >= device_cus())
     return {F_HRING};
@@ -402,7 +402,7 @@ Pick pick_tuned(const ConvParams& p) {
     // 79 -> 69, 512->512 @40 55 -> 48, 1024->1024 @20 44 -> 39; 3x3 256->256 @40 86 -> 70, s2 256->256
     // @80 90 -> 77, 256->512 @40 157 -> 134, 512->1024 @20 146 -> 128.  Under 200 tiles (@20 with
     // cout <= 512) the persistent 256 x 256 ring loses (2048->512 @20 41 -> 59).  YV7_WIDE_PRING=0: off.
-    static const int wide = [] { const char* e = getenv("YV7_WIDE_PRING"); return e ? atoi(e) : 1; }();
+    static const int wide = env_int("YV7_WIDE_PRING", 1);
     // The 8-phase ring (conv_f16_p8_kernel) where it measured faster in-network (scripts/tune_ops.py,
     // one layer forced at a time, bs 32, us, dispatch before -> p8): 3x3 256->256 @40 76 -> 67, s2
     // 256->256 @80 79 -> 72, 256->512 @40 137 -> 126, 512->1024 @20 130 -> 114; 1x1 with K >= 1024:
@@ -413,7 +413,7 @@ Pick pick_tuned(const ConvParams& p) {
     // Weight-stationary 1x1 (K <= 256, 128 < cout <= 256, >= 80x80 at bs 32; tune_ops, us): 256->256
     // @160 213 -> 201, @80 70 -> 66 / 66 -> 65; narrower or lower-resolution 1x1 layers lose.
     // YV7_WS1=0: off.
-    static const int ws1 = [] { const char* e = getenv("YV7_WS1"); return e ? atoi(e) : 1; }();
+    static const int ws1 = env_int("YV7_WS1", 1);
     // Round 3: its N-split form (two blocks per 256-pixel tile, each holding one 128-channel half of the
     // weights, three activation stages in flight instead of two; tune_ops, us: 256->256 @160 197.6 ->
     // 188.9, @80 60.3 -> 59.8 and 62.1 -> 58.6, profiles/r3w_tune.txt).
@@ -478,11 +478,11 @@ hipError_t launch_pick(const ConvParams& p, const Pick& k, hipStream_t st) {
     case F_RING: return launch_ring(p, k.cfg, k.S, st);
     case F_PRING: return launch_pring(p, k.cfg, st);
     case F_P8: return launch_p8(p, k.cfg, st);
-    case F_DET: return launch_det_pring(p, device_cus(), st);
+    case F_DET: return launch_det_pring(p, st);
     case F_LR: return launch_conv_lr(p, k.cfg, st);
-    case F_S2: return launch_conv_s2(p, k.cfg, device_cus(), st);
-    case F_W1: return launch_conv_w1(p, k.cfg, device_cus(), st);
-    case F_HRING: return launch_conv_hring(p, device_cus(), st);
+    case F_S2: return launch_conv_s2(p, k.cfg, st);
+    case F_W1: return launch_conv_w1(p, k.cfg, st);
+    case F_HRING: return launch_conv_hring(p, st);
     case F_WS64: return launch_conv_ws64(p, st);
     case F_HALO: return launch_conv_halo(p, st);
     case F_INVALID: break;

@@ -1,7 +1,7 @@
 // Device helpers shared by the fp16 implicit-GEMM conv kernels (conv_f16_ring.hip, conv_f16_pring.hip,
-// conv_f16_p8.hip, conv_det.hip): tile constants, the LDS swizzle, LDS-DMA, and the pixel / K walks
-// that turn operand addressing into per-lane offsets computed once plus scalar steps.  conv_f16.hip's
-// header describes the GEMM view they serve.
+// conv_f16_p8.hip, conv_det.hip): tile constants, the LDS swizzle, and the pixel / K walks that turn
+// operand addressing into per-lane offsets computed once plus scalar steps (LDS-DMA itself, dma16, is in
+// yv7_kernels.h).  conv_f16.hip's header describes the GEMM view they serve.
 #pragma once
 #include "yv7_kernels.h"
 
@@ -12,14 +12,8 @@ namespace {
 constexpr int NT = 256;
 constexpr int BKE = 64;    // K elements per step
 constexpr int ROWB = 128;  // LDS bytes per tile row
-constexpr uint32_t OOB = 0x80000000u;  // a buffer offset past every tensor: the load returns zeros
 
 __device__ __forceinline__ int swz(int row, int chunk) { return chunk ^ (row & 7); }
-
-// 16 bytes per lane from a buffer straight into LDS (lane-linear at the wave-uniform `lds` base)
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, void* lds, uint32_t vo, uint32_t so) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds, 16, vo, so, 0, 0);
-}
 
 // Output pixel m -> (b, ho, wo) once, then stepped: rows a thread moves are `step` pixels apart.
 // Rows past M walk into image B, whose offsets lie beyond the input buffer (zeros).

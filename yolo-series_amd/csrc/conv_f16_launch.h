@@ -3,35 +3,9 @@
 // non-template launch function per kernel, selected by a row of the family's table below: the tables
 // list every instantiation the library holds.  An unknown row is hipErrorInvalidValue.
 #pragma once
-#include <type_traits>
-#include <utility>
-
 #include "yv7_kernels.h"
 
 namespace yv7 {
-
-int device_cus();   // CUs of the current device (conv_f16.hip)
-
-// Calls f(std::integral_constant<int, ACT>) with the layer's activation as a compile-time constant: the
-// host side of with_act (yv7_kernels.h), for launchers whose kernel takes ACT as a template parameter.
-template <typename F>
-hipError_t launch_with_act(int act, F&& f) {
-  if (act == 1) return f(std::integral_constant<int, 1>{});
-  if (act == 2) return f(std::integral_constant<int, 2>{});
-  return f(std::integral_constant<int, 0>{});
-}
-
-// Calls f(std::integral_constant<int, row>) for 0 <= row < N: a table row as a compile-time constant.
-template <typename F, int... I>
-hipError_t launch_with_row_(int row, F&& f, std::integer_sequence<int, I...>) {
-  hipError_t e = hipErrorInvalidValue;
-  (void)((row == I && ((e = f(std::integral_constant<int, I>{})), true)) || ...);
-  return e;
-}
-template <int N, typename F>
-hipError_t launch_with_row(int row, F&& f) {
-  return launch_with_row_(row, static_cast<F&&>(f), std::make_integer_sequence<int, N>{});
-}
 
 // `one` of a row: the 1x1 / stride-1 / pad-0 form (K walks channels only) is instantiated for ...
 enum OneForms { ONE_BOTH = -1, ONE_NEVER = 0, ONE_ONLY = 1 };
@@ -89,7 +63,7 @@ hipError_t launch_p8(const ConvParams& p, int cfg, hipStream_t st);
 // conv_det.hip: the persistent Detect heads (conv_det_pring_kernel, conv_det_1tile_kernel,
 // conv_det_rw_kernel); launch_det_pring picks among them and reads p.variant for their forced forms / hooks
 bool det_pring_supported(const ConvParams& p);
-hipError_t launch_det_pring(const ConvParams& p, int cus, hipStream_t st);
+hipError_t launch_det_pring(const ConvParams& p, hipStream_t st);
 
 // A kernel configuration of the fp16 CONV dispatch the ABI may force (yv7_set_op_variant), as opposed
 // to a microbenchmark hook or no variant at all: read from the dispatch's forced-variant table.

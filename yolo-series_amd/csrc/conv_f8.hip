@@ -25,22 +25,7 @@ namespace {
 typedef int v8i __attribute__((ext_vector_type(8)));
 constexpr int ROWB8 = 128;   // LDS bytes per tile row per K step (128 fp8)
 
-__device__ __forceinline__ void dma16_f8(__amdgpu_buffer_rsrc_t r, void* lds, uint32_t vo, uint32_t so) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds, 16, vo, so, 0, 0);
-}
-
 __device__ __forceinline__ int swz8(int row, int chunk) { return chunk ^ (row & 7); }
-
-int cu_count() {
-  static const int n = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) !=
-                                                 hipSuccess || v <= 0)
-      v = 256;
-    return v;
-  }();
-  return n;
-}
 
 // ---- quantization: bordered fp16 NHWC slice -> dense e4m3 [M][kp]
 __global__ __launch_bounds__(256) void quant_f8_kernel(const _Float16* __restrict__ x, int B, int H, int W, int xc,
@@ -154,7 +139,7 @@ __global__ __launch_bounds__(64 * WM * WN, (STAGES * (BM + BN) * ROWB8 <= 76 * 1
     unsigned char* Bs = As + BN * ROWB8;                 // activations (MFMA B operand), BM rows
     const uint32_t so = (uint32_t)ikt * 128;
 #pragma unroll
-    for (int j = 0; j < RB; ++j) dma16_f8(wr, As + (j * NW + wave) * 8 * ROWB8, b_off[j], so);
+    for (int j = 0; j < RB; ++j) dma16(wr, As + (j * NW + wave) * 8 * ROWB8, b_off[j], so);
     if constexpr (XF16) {
       // channels [ikt * 128 + 16 chunk, + 16) of each row: two 16-byte fp16 loads (zeros past cin)
       const int c0 = ikt * 128 + q_chunk * 16;
@@ -168,7 +153,7 @@ __global__ __launch_bounds__(64 * WM * WN, (STAGES * (BM + BN) * ROWB8 <= 76 * 1
       }
     } else {
 #pragma unroll
-      for (int j = 0; j < RA; ++j) dma16_f8(xr, Bs + (j * NW + wave) * 8 * ROWB8, a_off[j], so);
+      for (int j = 0; j < RA; ++j) dma16(xr, Bs + (j * NW + wave) * 8 * ROWB8, a_off[j], so);
     }
     ++ig;
     if (++ikt == nk) { ikt = 0; ++it; }
@@ -353,13 +338,13 @@ __global__ __launch_bounds__(64 * WM * WN, (STAGES * (BM + BN) * ROWB8 <= 76 * 1
 template <int BM, int BN, int WM, int WN, int STAGES, bool XF16>
 hipError_t launch_f8(const F8ConvParams& p, int occ, hipStream_t st) {
   const long T = (long)((p.M + BM - 1) / BM) * ((p.cout + BN - 1) / BN);
-  const long cap = (long)cu_count() * occ;
+  const long cap = (long)device_cus() * occ;
   const int grid = (int)(T < cap ? T : cap);
   const dim3 blk(64 * WM * WN);
-  if (p.act == 1) YV7_LAUNCH((conv_f8_kernel<BM, BN, WM, WN, STAGES, 1, XF16>), dim3(grid), blk, 0, st, p);
-  else if (p.act == 2) YV7_LAUNCH((conv_f8_kernel<BM, BN, WM, WN, STAGES, 2, XF16>), dim3(grid), blk, 0, st, p);
-  else YV7_LAUNCH((conv_f8_kernel<BM, BN, WM, WN, STAGES, 0, XF16>), dim3(grid), blk, 0, st, p);
-  return hipGetLastError();
+  return launch_with_act(p.act, [&](auto A) {
+    YV7_LAUNCH((conv_f8_kernel<BM, BN, WM, WN, STAGES, decltype(A)::value, XF16>), dim3(grid), blk, 0, st, p);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace

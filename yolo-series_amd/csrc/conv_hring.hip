@@ -30,11 +30,6 @@ constexpr int CK = 32;                 // channels per phase (one MFMA K step)
 constexpr int ROWB = CK * 2;           // 64 bytes per LDS row
 constexpr int PPW = 3;                 // patch DMA pieces per wave per chunk (24 pieces: 21 rows of 16 pixels + 3 dummies)
 constexpr int NTH = 512;
-constexpr uint32_t OOB = 0x80000000u;  // a buffer offset past every tensor: DMA writes zeros
-
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, void* lds, uint32_t vo, uint32_t so) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds, 16, vo, so, 0, 0);
-}
 
 // The counted waits assume each wave's vector-memory ops issue exactly as written: every dummy DMA
 // present (identical dummies to one LDS address were merged by dead-store elimination — one op
@@ -43,12 +38,6 @@ __device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, void* lds, uint3
 // slots, and this compiler fence (no instruction) keeps the groups from being scheduled across
 // each other.
 __device__ __forceinline__ void dma_fence() { asm volatile("" ::: "memory"); }
-
-template <int N>
-__device__ __forceinline__ void vmwait() {
-  static_assert(N >= 0 && N < 64, "vmcnt range");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 // ---------------------------------------------------------------------------------------------
 // Halo ring, column-group form (variant 262).  Measured on round 3's first form (one tap per phase,
@@ -373,11 +362,12 @@ bool hring_supported(const ConvParams& p) {
 }
 
 // the column-group halo ring (variant 262)
-hipError_t launch_conv_hring(const ConvParams& p, int cus, hipStream_t st) {
+hipError_t launch_conv_hring(const ConvParams& p, hipStream_t st) {
   if (!hring_supported(p)) return hipErrorInvalidValue;
   // balanced persistent grid: every block the same number of tiles (the rest of the CUs stay free for
   // other streams' kernels rather than running a short last round)
   const long T = (long)p.B * (p.Ho / TS) * (p.Wo / TS) * ((p.cout + 127) / 128);
+  const int cus = device_cus();
   const long per = (T + cus - 1) / cus;
   const int grid = (int)((T + per - 1) / per);
   if (p.act == 1 && p.variant >= 911 && p.variant <= 914) {   // microbenchmark hooks (convbench only)
@@ -387,10 +377,10 @@ hipError_t launch_conv_hring(const ConvParams& p, int cus, hipStream_t st) {
     else YV7_LAUNCH((conv3x3_hring2_kernel<1, 4>), dim3(grid), dim3(NTH), 0, st, p);
     return hipGetLastError();
   }
-  if (p.act == 1) YV7_LAUNCH((conv3x3_hring2_kernel<1>), dim3(grid), dim3(NTH), 0, st, p);
-  else if (p.act == 2) YV7_LAUNCH((conv3x3_hring2_kernel<2>), dim3(grid), dim3(NTH), 0, st, p);
-  else YV7_LAUNCH((conv3x3_hring2_kernel<0>), dim3(grid), dim3(NTH), 0, st, p);
-  return hipGetLastError();
+  return launch_with_act(p.act, [&](auto A) {
+    YV7_LAUNCH((conv3x3_hring2_kernel<decltype(A)::value>), dim3(grid), dim3(NTH), 0, st, p);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace yv7

@@ -35,7 +35,6 @@ namespace {
 
 constexpr int FI = 4, FC = 4;   // MFMA pixel fragment: 4 images x 4 columns
 constexpr int CK = 32;          // channels per chunk (one MFMA K step)
-constexpr uint32_t OOB = 0x80000000u;
 
 __host__ __device__ constexpr int swz(int img) { return (0x1320 >> (4 * img)) & 3; }
 
@@ -78,16 +77,15 @@ struct LrGeo {
 // latency is not what these layers wait on; nor did the weights four to seven column steps ahead (PD 4-7
 // on rows 0 / 1 / 6, profiles/r6_lr_pd/tune.txt: 22.7 -> 23.5, 61.1 -> 65.8, 38.8 -> 41.6 us).  The PF column
 // stays (1 everywhere).
-#define LR_CFGS(X)                                                                                   \
-  X(0, 1, 4, 2, 5, 3, 1, 1) X(1, 1, 4, 1, 5, 3, 1, 1) X(2, 1, 4, 2, 4, 3, 1, 1) X(3, 1, 4, 1, 4, 3, 1, 1)          \
-  X(4, 1, 4, 2, 4, 3, 2, 1) X(5, 1, 4, 2, 10, 2, 1, 1) X(6, 1, 4, 1, 10, 3, 1, 1) X(7, 1, 4, 2, 5, 3, 2, 1)        \
-  X(8, 1, 4, 2, 8, 2, 2, 1) X(9, 1, 4, 1, 10, 3, 2, 1)
-#define LR_ROW(i, wm, wn, tn, tm, pd, s, pf) {wm, wn, tn, tm, pd, s, pf},
-constexpr int LR_CFG[][7] = {LR_CFGS(LR_ROW)};
-constexpr int LR_NCFG = sizeof(LR_CFG) / sizeof(LR_CFG[0]);
+struct LrRow { int wm, wn, tn, tm, pd, s, pf; };
+constexpr LrRow lr_rows[] = {
+    {1, 4, 2, 5, 3, 1, 1}, {1, 4, 1, 5, 3, 1, 1},  {1, 4, 2, 4, 3, 1, 1},  {1, 4, 1, 4, 3, 1, 1},
+    {1, 4, 2, 4, 3, 2, 1}, {1, 4, 2, 10, 2, 1, 1}, {1, 4, 1, 10, 3, 1, 1}, {1, 4, 2, 5, 3, 2, 1},
+    {1, 4, 2, 8, 2, 2, 1}, {1, 4, 1, 10, 3, 2, 1}};
+constexpr int LR_NCFG = sizeof(lr_rows) / sizeof(lr_rows[0]);
 
 // One output tile: images b0 .. b0 + 3, rows y0 .. y0 + TH - 1, columns x0 .. x0 + 3, channels n0 .. n0 + BN - 1
-// (the body of conv3x3_lr_kernel, shared with the chain kernel of conv_chain.hip).  CPL / CPS: cache policy of
+// (the body of conv3x3_lr_kernel, shared with conv3x3_chain_kernel below).  CPL / CPS: cache policy of
 // the patch loads / output stores (0, or CPOL_SC1 for an in-launch hand-off between chained layers); `ready`
 // runs before the first load of the tile (the chain kernel waits there for the producing layer's rows).
 template <int WM, int WN, int TN, int TM, int NCH, int ACT, int PD, int S, int PF = 1, int CPL = 0, int CPS = 0,
@@ -323,8 +321,8 @@ constexpr int CH_HEAD = 0, CH_DONE = 32, CH_ERR = 64, CH_BAND0 = 96, CH_LINE = 3
 
 template <int C>
 struct LrCfg {
-  static constexpr int WM = LR_CFG[C][0], WN = LR_CFG[C][1], TN = LR_CFG[C][2], TM = LR_CFG[C][3],
-                       PD = LR_CFG[C][4], S = LR_CFG[C][5], PF = LR_CFG[C][6];
+  static constexpr int WM = lr_rows[C].wm, WN = lr_rows[C].wn, TN = lr_rows[C].tn, TM = lr_rows[C].tm,
+                       PD = lr_rows[C].pd, S = lr_rows[C].s, PF = lr_rows[C].pf;
   static constexpr int TH = WM * TM, BN = WN * TN * 16, NT = 64 * WM * WN;
   static constexpr int PB = LrGeo<WM, WN, TM, S>::PB;
 };
@@ -344,8 +342,8 @@ __host__ __device__ inline ChainGeo chain_geo(const ChainParams& c) {
   for (int l = 0; l < CHAIN_MAX; ++l) {
     const int cfg = l == 0 ? c.cfg0 : c.cfg1;
     const bool on = l < c.nl;
-    g.th[l] = LR_CFG[cfg][0] * LR_CFG[cfg][3];
-    g.bn[l] = LR_CFG[cfg][1] * LR_CFG[cfg][2] * 16;
+    g.th[l] = lr_rows[cfg].wm * lr_rows[cfg].tm;
+    g.bn[l] = lr_rows[cfg].wn * lr_rows[cfg].tn * 16;
     g.nrg[l] = on ? c.p[l].Ho / g.th[l] : 0;
     g.nN[l] = on ? (c.p[l].cout + g.bn[l] - 1) / g.bn[l] : 0;
     g.t0[l + 1] = g.t0[l] + g.nig * g.nrg[l] * g.ncg * g.nN[l];
@@ -466,9 +464,11 @@ __global__ __launch_bounds__(256, 3) void conv3x3_chain_kernel(const ChainParams
 // runtime gives a chain 80 x 64 tiles where the single-layer dispatch would take 80 x 128 (equal there
 // per layer, profiles/r4lr/tune3.txt; twice the tasks for the queue, and the 128-channel form's 160
 // VGPRs leave no room for the chain's state at 3 blocks per CU)
-#define CHAIN_FORMS(X)                                                                                \
-  X(1, 8, 1, 8) X(1, 16, 1, 8) X(1, 8, 1, 4) X(1, 12, 1, 12) X(3, 16, 3, 16) X(3, 12, 3, 16) X(1, 24, 1, 12) \
-  X(1, 6, 1, 6) X(1, 12, 1, 6) X(3, 24, 3, 16) X(1, 16, 1, 16) X(1, 4, 1, 4)
+struct ChainForm { int cfg0, nch0, cfg1, nch1; };
+constexpr ChainForm chain_forms[] = {
+    {1, 8, 1, 8}, {1, 16, 1, 8}, {1, 8, 1, 4},   {1, 12, 1, 12}, {3, 16, 3, 16}, {3, 12, 3, 16}, {1, 24, 1, 12},
+    {1, 6, 1, 6}, {1, 12, 1, 6}, {3, 24, 3, 16}, {1, 16, 1, 16}, {1, 4, 1, 4}};
+constexpr int NCHAIN = sizeof(chain_forms) / sizeof(chain_forms[0]);
 
 // Fragment packing: out[((nf * nch + c) * T + tap) * 512 + lane * 8 + e] =
 // w[(nf * 16 + lane % 16) * kpad + tap * cin + c * 32 + (lane / 16) * 8 + e] — the MFMA A operand of
@@ -488,14 +488,15 @@ __global__ void pack_frag_kernel(const _Float16* w, int kpad, int cin, int nfrag
   }
 }
 
-template <int WM, int WN, int TN, int TM, int PD, int S, int PF, int NCH>
+template <int ROW, int NCH>
 hipError_t launch_cfg(const ConvParams& p, hipStream_t st) {
-  constexpr int TH = TM * WM, BN = WN * TN * 16;
+  constexpr LrRow r = lr_rows[ROW];
+  constexpr int TH = r.tm * r.wm, BN = r.wn * r.tn * 16;
   const long P = (long)((p.B + FI - 1) / FI) * (p.Ho / TH) * (p.Wo / FC);
   const int nN = (p.cout + BN - 1) / BN;
   // N groups over the XCDs: the fewest (a divisor of both 8 and nN) that keep one XCD's weight share
   // under 2.5 MiB (YV7_LR_NGX forces a value for A/B runs)
-  static const int force = [] { const char* e = getenv("YV7_LR_NGX"); return e ? atoi(e) : 0; }();
+  static const int force = env_int("YV7_LR_NGX", 0);
   const double wbytes = (double)p.cout * 9 * p.cin * 2;
   int ngx = 1;
   if (force > 0) {
@@ -506,26 +507,26 @@ hipError_t launch_cfg(const ConvParams& p, hipStream_t st) {
   if (ngx < 1 || 8 % ngx || nN % ngx) ngx = 1;
   const int npx = 8 / ngx, nsl = nN / ngx;
   const long grid = 8L * nsl * ((P + npx - 1) / npx);
-  if (p.act == 1) YV7_LAUNCH((conv3x3_lr_kernel<WM, WN, TN, TM, NCH, 1, PD, S, PF>), dim3((unsigned)grid), dim3(64 * WM * WN), 0, st, p, ngx);
-  else if (p.act == 2) YV7_LAUNCH((conv3x3_lr_kernel<WM, WN, TN, TM, NCH, 2, PD, S, PF>), dim3((unsigned)grid), dim3(64 * WM * WN), 0, st, p, ngx);
-  else YV7_LAUNCH((conv3x3_lr_kernel<WM, WN, TN, TM, NCH, 0, PD, S, PF>), dim3((unsigned)grid), dim3(64 * WM * WN), 0, st, p, ngx);
-  return hipGetLastError();
+  return launch_with_act(p.act, [&](auto A) {
+    YV7_LAUNCH((conv3x3_lr_kernel<r.wm, r.wn, r.tn, r.tm, NCH, decltype(A)::value, r.pd, r.s, r.pf>), dim3((unsigned)grid),
+               dim3(64 * r.wm * r.wn), 0, st, p, ngx);
+    return hipGetLastError();
+  });
 }
 
-template <int WM, int WN, int TN, int TM, int PD, int S, int PF>
+template <int ROW>
 hipError_t launch_nch(const ConvParams& p, hipStream_t st) {
   switch (p.cin / CK) {
-    case 2: return launch_cfg<WM, WN, TN, TM, PD, S, PF, 2>(p, st);
-    case 4: return launch_cfg<WM, WN, TN, TM, PD, S, PF, 4>(p, st);
-    case 6: return launch_cfg<WM, WN, TN, TM, PD, S, PF, 6>(p, st);
-    case 8: return launch_cfg<WM, WN, TN, TM, PD, S, PF, 8>(p, st);
-    case 12: return launch_cfg<WM, WN, TN, TM, PD, S, PF, 12>(p, st);
-    case 16: return launch_cfg<WM, WN, TN, TM, PD, S, PF, 16>(p, st);
-    case 24: return launch_cfg<WM, WN, TN, TM, PD, S, PF, 24>(p, st);
+    case 2: return launch_cfg<ROW, 2>(p, st);
+    case 4: return launch_cfg<ROW, 4>(p, st);
+    case 6: return launch_cfg<ROW, 6>(p, st);
+    case 8: return launch_cfg<ROW, 8>(p, st);
+    case 12: return launch_cfg<ROW, 12>(p, st);
+    case 16: return launch_cfg<ROW, 16>(p, st);
+    case 24: return launch_cfg<ROW, 24>(p, st);
   }
   return hipErrorInvalidValue;
 }
-
 
 }  // namespace
 
@@ -539,10 +540,10 @@ hipError_t pack_frag(const void* w, int kpad, int cin, int cout, int taps, void*
   return hipGetLastError();
 }
 
-// cfg: LR_CFG row (variants 270 + cfg)
+// cfg: lr_rows row (variants 270 + cfg)
 bool lr_supported(const ConvParams& p, int cfg) {
   if (cfg < 0 || cfg >= LR_NCFG) return false;
-  const int th = LR_CFG[cfg][0] * LR_CFG[cfg][3], S = LR_CFG[cfg][5];
+  const int th = lr_rows[cfg].wm * lr_rows[cfg].tm, S = lr_rows[cfg].s;
   const int nch = p.cin / CK;
   const bool geom = S == 1 ? (p.Ho == p.H && p.Wo == p.W) : (p.H % 2 == 0 && p.W % 2 == 0 && p.Ho == p.H / 2 && p.Wo == p.W / 2);
   return p.wf && p.k == 3 && p.s == S && p.pad == 1 && !p.pool && p.cin % CK == 0 && geom &&
@@ -553,24 +554,17 @@ bool lr_supported(const ConvParams& p, int cfg) {
 
 hipError_t launch_conv_lr(const ConvParams& p, int cfg, hipStream_t st) {
   if (!lr_supported(p, cfg)) return hipErrorInvalidValue;
-  switch (cfg) {
-#define LR_CASE(i, wm, wn, tn, tm, pd, s, pf) \
-  case i: return launch_nch<wm, wn, tn, tm, pd, s, pf>(p, st);
-    LR_CFGS(LR_CASE)
-#undef LR_CASE
-  }
-  return hipErrorInvalidValue;
+  return launch_with_row<LR_NCFG>(cfg, [&](auto I) { return launch_nch<decltype(I)::value>(p, st); });
 }
 
+// the chain's row of chain_forms, or -1
 static int chain_form(const ChainParams& c) {
   const int n0 = c.p[0].cin / CK, n1 = c.nl > 1 ? c.p[1].cin / CK : 0;
-  int id = 0, k = 0;
-#define CHAIN_ID(a, b, cc, d) \
-  if (id == 0 && c.cfg0 == a && n0 == b && c.cfg1 == cc && n1 == d) id = k + 1; \
-  ++k;
-  CHAIN_FORMS(CHAIN_ID)
-#undef CHAIN_ID
-  return id - 1;
+  for (int k = 0; k < NCHAIN; ++k) {
+    const ChainForm& f = chain_forms[k];
+    if (c.cfg0 == f.cfg0 && n0 == f.nch0 && c.cfg1 == f.cfg1 && n1 == f.nch1) return k;
+  }
+  return -1;
 }
 
 bool chain_supported(const ChainParams& c) {
@@ -595,29 +589,16 @@ long chain_tasks(const ChainParams& c) { return chain_geo(c).t0[c.nl]; }
 
 hipError_t launch_conv_chain(const ChainParams& c, hipStream_t st) {
   if (!chain_supported(c) || !c.ctr) return hipErrorInvalidValue;
-  static const int cus = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        v <= 0)
-      v = 256;
-    return v;
-  }();
   const ChainGeo g = chain_geo(c);
   const long total = g.t0[c.nl];
-  const int grid = (int)(total < 3L * cus ? total : 3L * cus);   // 3 blocks per CU at most are resident
-  const int form = chain_form(c), act = c.p[0].act;
-  int k = 0;
-#define CHAIN_CASE(a, b, cc, d)                                                                              \
-  if (form == k) {                                                                                           \
-    if (act == 1) YV7_LAUNCH((conv3x3_chain_kernel<a, b, cc, d, 1>), dim3(grid), dim3(256), 0, st, c);       \
-    else if (act == 2) YV7_LAUNCH((conv3x3_chain_kernel<a, b, cc, d, 2>), dim3(grid), dim3(256), 0, st, c);  \
-    else YV7_LAUNCH((conv3x3_chain_kernel<a, b, cc, d, 0>), dim3(grid), dim3(256), 0, st, c);                \
-    return hipGetLastError();                                                                                \
-  }                                                                                                          \
-  ++k;
-  CHAIN_FORMS(CHAIN_CASE)
-#undef CHAIN_CASE
-  return hipErrorInvalidValue;
+  const int grid = (int)(total < 3L * device_cus() ? total : 3L * device_cus());   // 3 blocks per CU at most are resident
+  return launch_with_row<NCHAIN>(chain_form(c), [&](auto I) {
+    constexpr ChainForm f = chain_forms[decltype(I)::value];
+    return launch_with_act(c.p[0].act, [&](auto A) {
+      YV7_LAUNCH((conv3x3_chain_kernel<f.cfg0, f.nch0, f.cfg1, f.nch1, decltype(A)::value>), dim3(grid), dim3(256), 0, st, c);
+      return hipGetLastError();
+    });
+  });
 }
 
 }  // namespace yv7

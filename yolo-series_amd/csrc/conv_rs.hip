@@ -301,10 +301,10 @@ __global__ __launch_bounds__(NTH, 1) void conv1x1_rs_kernel(const ConvParams p, 
 
 template <int KS, int NF, bool POOL>
 hipError_t launch_ks(const ConvParams& p, const Conv1x1Pooled& q, int grid, hipStream_t st) {
-  if (p.act == 1) YV7_LAUNCH((conv1x1_rs_kernel<KS, NF, POOL, 1>), dim3(grid), dim3(NTH), 0, st, p, q);
-  else if (p.act == 2) YV7_LAUNCH((conv1x1_rs_kernel<KS, NF, POOL, 2>), dim3(grid), dim3(NTH), 0, st, p, q);
-  else YV7_LAUNCH((conv1x1_rs_kernel<KS, NF, POOL, 0>), dim3(grid), dim3(NTH), 0, st, p, q);
-  return hipGetLastError();
+  return launch_with_act(p.act, [&](auto A) {
+    YV7_LAUNCH((conv1x1_rs_kernel<KS, NF, POOL, decltype(A)::value>), dim3(grid), dim3(NTH), 0, st, p, q);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace
@@ -323,16 +323,9 @@ bool conv1x1_rs_supported(const ConvParams& p, const Conv1x1Pooled* q) {
 
 hipError_t launch_conv1x1_rs(const ConvParams& p, const Conv1x1Pooled* q, hipStream_t st) {
   if (!conv1x1_rs_supported(p, q)) return hipErrorInvalidValue;
-  static const int cus = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) !=
-                                                 hipSuccess || v <= 0)
-      v = 256;
-    return v;
-  }();
   const long U = (long)p.B * (p.H / 2) * (p.W / 16);
   const long G = (U + 7) / 8;
-  const int grid = (int)(G < cus ? G : cus);
+  const int grid = (int)(G < device_cus() ? G : device_cus());
   const Conv1x1Pooled none{};
   const bool two = p.cout > 128;
   if (q) return p.cin == 128 ? launch_ks<4, 1, true>(p, *q, grid, st) : launch_ks<8, 1, true>(p, *q, grid, st);

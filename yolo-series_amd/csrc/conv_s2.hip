@@ -5,7 +5,7 @@
 // yolov7-w6.yaml's 128-input stride-2 convs (:29 P3 entry 128->256 @320, and its head's).
 // y = act(conv2d(x, W', b', s=2, pad=1)).  The same kernel with S = 1 (configurations 5-8) serves the
 // large 64- and 128-input stride-1 3x3 layers (yolov7.yaml:19 64->64 @320, the ELAN 3x3 128->128 @80 and
-// the head's RepConv 128->256 @80; the dispatch rule in conv_f16.hip launch_conv_f16).
+// the head's RepConv 128->256 @80; the dispatch rule in conv_f16.hip pick_tuned).
 //
 // Why: the stride-2 layers were the furthest below their roofline (yolov7: 517 us
 // against a 174 us roof; 64->128 s2 @320 alone 190 us against 79).  Their implicit-GEMM rings stage one
@@ -44,17 +44,6 @@ namespace {
 
 constexpr int FI = 4, FC = 4;   // MFMA pixel fragment: 4 images x 4 columns
 constexpr int DC = 64;          // channels per DMA chunk (one 128-byte line per pixel; two MFMA K steps)
-constexpr uint32_t OOB = 0x80000000u;
-
-template <int N>
-__device__ __forceinline__ void vmwait() {
-  static_assert(N >= 0 && N < 64, "vmcnt range");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, void* lds, uint32_t vo, uint32_t so) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds, 16, vo, so, 0, 0);
-}
 
 // position swizzle of a pixel's eight 16-byte parts (S = 2: by its column slot; S = 1, whose patch rows
 // have an even pixel count, by image and slot — scripts/s2_swizzle_check.py, s1_swizzle_check.py)
@@ -331,61 +320,53 @@ __global__ __launch_bounds__(512, 2) void conv3x3s2_rw_kernel(const ConvParams p
 // tile configurations (variants 280 + row): {NCH, TN, TM, PG, NG, NS, STG, S}.  0-4: stride 2 (cin 64 /
 // 128); 5-8: stride 1 (the same machinery for the 64 / 128-input 3x3 layers: cin 64 with 64 output
 // channels = conv_ws.hip's layers, cin 128).
-#define S2_CFGS(X)                                                                                             \
-  X(0, 2, 2, 2, 2, 4, 3, 0, 2) X(1, 2, 2, 4, 2, 4, 2, 0, 2) X(2, 4, 1, 4, 1, 8, 3, 0, 2) X(3, 4, 1, 2, 1, 8, 4, 1, 2) \
-  X(4, 4, 1, 8, 1, 8, 2, 0, 2) X(5, 2, 2, 2, 4, 2, 4, 1, 1) X(6, 2, 2, 4, 4, 2, 2, 0, 1) X(7, 4, 1, 4, 1, 8, 4, 1, 1) \
-  X(8, 4, 1, 8, 1, 8, 4, 1, 1)
-#define S2_ROW(i, nch, tn, tm, pg, ng, ns, stg, st) {nch, tn, tm, pg, ng, ns, stg, st},
-constexpr int S2_CFG[][8] = {S2_CFGS(S2_ROW)};
-constexpr int S2_NCFG = sizeof(S2_CFG) / sizeof(S2_CFG[0]);
+struct S2Row { int nch, tn, tm, pg, ng, ns, stg, s; };
+constexpr S2Row s2_rows[] = {
+    {2, 2, 2, 2, 4, 3, 0, 2}, {2, 2, 4, 2, 4, 2, 0, 2}, {4, 1, 4, 1, 8, 3, 0, 2}, {4, 1, 2, 1, 8, 4, 1, 2},
+    {4, 1, 8, 1, 8, 2, 0, 2}, {2, 2, 2, 4, 2, 4, 1, 1}, {2, 2, 4, 4, 2, 2, 0, 1}, {4, 1, 4, 1, 8, 4, 1, 1},
+    {4, 1, 8, 1, 8, 4, 1, 1}};
+constexpr int S2_NCFG = sizeof(s2_rows) / sizeof(s2_rows[0]);
 
-template <int NCH, int TN, int TM, int PG, int NG, int NS, int STG, int S, int HOOK = 0>
-hipError_t launch_cfg(const ConvParams& p, int cus, hipStream_t st) {
-  using G = S2Geo<NCH, TN, TM, PG, NG, NS, STG, S>;
+template <int ROW, int HOOK = 0>
+hipError_t launch_row(const ConvParams& p, hipStream_t st) {
+  constexpr S2Row r = s2_rows[ROW];
+  using G = S2Geo<r.nch, r.tn, r.tm, r.pg, r.ng, r.ns, r.stg, r.s>;
   const int nN = (p.cout + G::BN - 1) / G::BN;
-  const long T = (long)((p.B + FI - 1) / FI) * (p.Ho / TM) * (p.Wo / (FC * PG));
+  const long T = (long)((p.B + FI - 1) / FI) * (p.Ho / r.tm) * (p.Wo / (FC * r.pg));
   // persistent grid: a multiple of 8 * nN blocks (each XCD holds every N slice of its walk), at most one
   // block per CU, and no more virtual blocks than tiles (rounded to the XCD count)
-  long per = cus / (8 * nN);
+  long per = device_cus() / (8 * nN);
   const long need = (T + 7) / 8;
   if (per > need) per = need;
   if (per < 1) per = 1;
   const int grid = (int)(per * 8 * nN);
   if (HOOK) {
-    YV7_LAUNCH((conv3x3s2_rw_kernel<NCH, TN, TM, PG, NG, NS, STG, S, 1, HOOK>), dim3(grid), dim3(512), 0, st, p, nN);
+    YV7_LAUNCH((conv3x3s2_rw_kernel<r.nch, r.tn, r.tm, r.pg, r.ng, r.ns, r.stg, r.s, 1, HOOK>), dim3(grid), dim3(512), 0, st, p, nN);
     return hipGetLastError();
   }
-  if (p.act == 1)
-    YV7_LAUNCH((conv3x3s2_rw_kernel<NCH, TN, TM, PG, NG, NS, STG, S, 1>), dim3(grid), dim3(512), 0, st, p, nN);
-  else if (p.act == 2)
-    YV7_LAUNCH((conv3x3s2_rw_kernel<NCH, TN, TM, PG, NG, NS, STG, S, 2>), dim3(grid), dim3(512), 0, st, p, nN);
-  else
-    YV7_LAUNCH((conv3x3s2_rw_kernel<NCH, TN, TM, PG, NG, NS, STG, S, 0>), dim3(grid), dim3(512), 0, st, p, nN);
-  return hipGetLastError();
+  return launch_with_act(p.act, [&](auto A) {
+    YV7_LAUNCH((conv3x3s2_rw_kernel<r.nch, r.tn, r.tm, r.pg, r.ng, r.ns, r.stg, r.s, decltype(A)::value>), dim3(grid), dim3(512), 0, st, p, nN);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace
 
-// cfg: S2_CFG row (variants 280 + cfg)
+// cfg: s2_rows row (variants 280 + cfg)
 bool s2_supported(const ConvParams& p, int cfg) {
   if (cfg < 0 || cfg >= S2_NCFG) return false;
-  const int nch = S2_CFG[cfg][0], tm = S2_CFG[cfg][2], pg = S2_CFG[cfg][3], S = S2_CFG[cfg][7];
+  const S2Row& r = s2_rows[cfg];
+  const int S = r.s;
   const bool geom = S == 2 ? (p.H % 2 == 0 && p.W % 2 == 0 && p.Ho == p.H / 2 && p.Wo == p.W / 2)
                            : (p.Ho == p.H && p.Wo == p.W);
-  return p.wf && p.k == 3 && p.s == S && p.pad == 1 && !p.pool && p.cin == nch * 32 && geom && p.Ho % tm == 0 &&
-         p.Wo % (FC * pg) == 0 && p.cout % 16 == 0 && p.cout <= 1024 && p.xoff % 8 == 0 && p.xc % 8 == 0 &&
+  return p.wf && p.k == 3 && p.s == S && p.pad == 1 && !p.pool && p.cin == r.nch * 32 && geom && p.Ho % r.tm == 0 &&
+         p.Wo % (FC * r.pg) == 0 && p.cout % 16 == 0 && p.cout <= 1024 && p.xoff % 8 == 0 && p.xc % 8 == 0 &&
          p.yoff % 8 == 0 && p.yc % 8 == 0;
 }
 
-hipError_t launch_conv_s2(const ConvParams& p, int cfg, int cus, hipStream_t st) {
+hipError_t launch_conv_s2(const ConvParams& p, int cfg, hipStream_t st) {
   if (!s2_supported(p, cfg)) return hipErrorInvalidValue;
-  switch (cfg) {
-#define S2_CASE(i, nch, tn, tm, pg, ng, ns, stg, st_) \
-  case i: return launch_cfg<nch, tn, tm, pg, ng, ns, stg, st_>(p, cus, st);
-    S2_CFGS(S2_CASE)
-#undef S2_CASE
-  }
-  return hipErrorInvalidValue;
+  return launch_with_row<S2_NCFG>(cfg, [&](auto I) { return launch_row<decltype(I)::value>(p, st); });
 }
 
 }  // namespace yv7

@@ -28,17 +28,6 @@ namespace yv7 {
 namespace {
 
 constexpr int DC = 64;          // channels per DMA chunk (one 128-byte line per pixel; two MFMA K steps)
-constexpr uint32_t OOB = 0x80000000u;
-
-template <int N>
-__device__ __forceinline__ void vmwait() {
-  static_assert(N >= 0 && N < 64, "vmcnt range");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, void* lds, uint32_t vo, uint32_t so) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds, 16, vo, so, 0, 0);
-}
 
 // bordered pixel index of output pixel m (H, W: the tensor's interior size; rW = 1 / W, rH = 1 / H)
 __device__ __forceinline__ uint32_t bpix(int m, int H, int W, float rW, float rH) {
@@ -292,59 +281,50 @@ __global__ __launch_bounds__(512, 2) void conv1x1_rw_kernel(const ConvParams p, 
 // STG, IC}.  0-2: an interval per 64-channel chunk (cin 128 / 256 / 512), no stagger; 3-5: an interval per
 // tile, stagger 1; 6-7: cin 256 with a 128-channel N slice (cfg 3's is 256: half its waves would compute
 // masked channels of a 128-output layer).
-#define W1_CFGS(X)                                                                                             \
-  X(0, 4, 8, 2, 8, 1, 4, 0, 1) X(1, 8, 4, 4, 2, 4, 8, 0, 1) X(2, 16, 2, 4, 2, 4, 8, 0, 1) X(3, 8, 4, 2, 2, 4, 4, 1, 4) \
-  X(4, 4, 8, 1, 8, 1, 4, 1, 2) X(5, 16, 2, 2, 1, 8, 4, 1, 8) X(6, 8, 4, 1, 4, 2, 4, 1, 4) X(7, 8, 2, 2, 2, 4, 4, 1, 4)
-#define W1_ROW(i, nch, tn, tpf, pg, ng, ns, stg, ic) {nch, tn, tpf, pg, ng, ns, stg, ic},
-constexpr int W1_CFG[][8] = {W1_CFGS(W1_ROW)};
-constexpr int W1_NCFG = sizeof(W1_CFG) / sizeof(W1_CFG[0]);
+struct W1Row { int nch, tn, tpf, pg, ng, ns, stg, ic; };
+constexpr W1Row w1_rows[] = {
+    {4, 8, 2, 8, 1, 4, 0, 1}, {8, 4, 4, 2, 4, 8, 0, 1}, {16, 2, 4, 2, 4, 8, 0, 1}, {8, 4, 2, 2, 4, 4, 1, 4},
+    {4, 8, 1, 8, 1, 4, 1, 2}, {16, 2, 2, 1, 8, 4, 1, 8}, {8, 4, 1, 4, 2, 4, 1, 4}, {8, 2, 2, 2, 4, 4, 1, 4}};
+constexpr int W1_NCFG = sizeof(w1_rows) / sizeof(w1_rows[0]);
 
-template <int NCH, int TN, int TPF, int PG, int NG, int NS, int STG, int IC, int HOOK = 0>
-hipError_t launch_cfg(const ConvParams& p, int cus, hipStream_t st) {
-  using G = W1Geo<NCH, TN, TPF, PG, NG, NS, STG, IC>;
+template <int ROW, int HOOK = 0>
+hipError_t launch_row(const ConvParams& p, hipStream_t st) {
+  constexpr W1Row r = w1_rows[ROW];
+  using G = W1Geo<r.nch, r.tn, r.tpf, r.pg, r.ng, r.ns, r.stg, r.ic>;
   const int nN = (p.cout + G::BN - 1) / G::BN;
   const long T = ((long)p.M + G::TPX - 1) / G::TPX;
-  long per = cus / (8 * nN);
+  long per = device_cus() / (8 * nN);
   const long need = (T + 7) / 8;
   if (per > need) per = need;
   if (per < 1) per = 1;
   const int grid = (int)(per * 8 * nN);
   if (HOOK) {
-    YV7_LAUNCH((conv1x1_rw_kernel<NCH, TN, TPF, PG, NG, NS, STG, IC, 1, HOOK>), dim3(grid), dim3(512), 0, st, p, nN);
+    YV7_LAUNCH((conv1x1_rw_kernel<r.nch, r.tn, r.tpf, r.pg, r.ng, r.ns, r.stg, r.ic, 1, HOOK>), dim3(grid), dim3(512), 0, st, p, nN);
     return hipGetLastError();
   }
-  if (p.act == 1)
-    YV7_LAUNCH((conv1x1_rw_kernel<NCH, TN, TPF, PG, NG, NS, STG, IC, 1>), dim3(grid), dim3(512), 0, st, p, nN);
-  else if (p.act == 2)
-    YV7_LAUNCH((conv1x1_rw_kernel<NCH, TN, TPF, PG, NG, NS, STG, IC, 2>), dim3(grid), dim3(512), 0, st, p, nN);
-  else
-    YV7_LAUNCH((conv1x1_rw_kernel<NCH, TN, TPF, PG, NG, NS, STG, IC, 0>), dim3(grid), dim3(512), 0, st, p, nN);
-  return hipGetLastError();
+  return launch_with_act(p.act, [&](auto A) {
+    YV7_LAUNCH((conv1x1_rw_kernel<r.nch, r.tn, r.tpf, r.pg, r.ng, r.ns, r.stg, r.ic, decltype(A)::value>), dim3(grid), dim3(512), 0, st, p, nN);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace
 
 bool w1_supported(const ConvParams& p, int cfg) {
   if (cfg < 0 || cfg >= W1_NCFG) return false;
-  return p.wf && p.k == 1 && p.s == 1 && p.pad == 0 && !p.pool && p.cin == W1_CFG[cfg][0] * 32 &&
+  return p.wf && p.k == 1 && p.s == 1 && p.pad == 0 && !p.pool && p.cin == w1_rows[cfg].nch * 32 &&
          p.H == p.Ho && p.W == p.Wo && (long)p.M < (1L << 24) && p.cout % 16 == 0 && p.cout <= 1024 &&
          p.xoff % 8 == 0 && p.xc % 8 == 0 && p.yoff % 8 == 0 && p.yc % 8 == 0;
 }
 
-hipError_t launch_conv_w1(const ConvParams& p, int cfg, int cus, hipStream_t st) {
+hipError_t launch_conv_w1(const ConvParams& p, int cfg, hipStream_t st) {
   if (!w1_supported(p, cfg)) return hipErrorInvalidValue;
   if (p.act == 1 && cfg == 1 && p.variant >= 299 && p.variant <= 301) {   // hooks (convbench)
-    if (p.variant == 299) return launch_cfg<8, 4, 4, 2, 4, 8, 0, 1, 2>(p, cus, st);
-    if (p.variant == 300) return launch_cfg<8, 4, 4, 2, 4, 8, 0, 1, 3>(p, cus, st);
-    return launch_cfg<8, 4, 4, 2, 4, 8, 0, 1, 4>(p, cus, st);
+    if (p.variant == 299) return launch_row<1, 2>(p, st);
+    if (p.variant == 300) return launch_row<1, 3>(p, st);
+    return launch_row<1, 4>(p, st);
   }
-  switch (cfg) {
-#define W1_CASE(i, nch, tn, tpf, pg, ng, ns, stg, ic) \
-  case i: return launch_cfg<nch, tn, tpf, pg, ng, ns, stg, ic>(p, cus, st);
-    W1_CFGS(W1_CASE)
-#undef W1_CASE
-  }
-  return hipErrorInvalidValue;
+  return launch_with_row<W1_NCFG>(cfg, [&](auto I) { return launch_row<decltype(I)::value>(p, st); });
 }
 
 }  // namespace yv7

@@ -48,10 +48,6 @@ constexpr int WTAP = CO * CI * 2;            // 8 KiB of weights per tap
 constexpr int LDS = 2 * PBUF + 9 * WTAP;     // 157,696 B
 typedef uint32_t u2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, void* lds, uint32_t vo, uint32_t so) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds, 16, vo, so, 0, 0);
-}
-
 // The layer's weights -> LDS once per block: tap t, out channel n, 16-byte slot s holds K chunk
 // s ^ (n & 7) of that tap.  A thread's 18 chunks go as two batches of 9 loads issued before their LDS
 // writes (as a load -> write loop, hipcc waited out one L2 round trip per chunk: 18 in a row before
@@ -597,17 +593,6 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_ws64r_kernel(const ConvParams p
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-int num_cus() {
-  static const int n = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) !=
-                                                 hipSuccess || v <= 0)
-      v = 256;
-    return v;
-  }();
-  return n;
-}
-
 }  // namespace
 
 bool ws64_supported(const ConvParams& p) {
@@ -619,7 +604,7 @@ bool ws64_supported(const ConvParams& p) {
 hipError_t launch_conv_ws64(const ConvParams& p, hipStream_t st) {
   if (!ws64_supported(p)) return hipErrorInvalidValue;
   const int T = p.B * (p.H / TS) * (p.W / TS);
-  const int grid = T < num_cus() ? T : num_cus();
+  const int grid = T < device_cus() ? T : device_cus();
   // microbenchmark hooks (scripts/convbench.hip only; the ABI never accepts them) on the column-pair form
   if (p.act == 1 && p.variant >= 12 && p.variant <= 16 && p.variant != 15) {
     if (p.variant == 12) YV7_LAUNCH((conv3x3_ws64_kernel<1, 12>), dim3(grid), dim3(NT), 0, st, p);
@@ -632,28 +617,22 @@ hipError_t launch_conv_ws64(const ConvParams& p, hipStream_t st) {
   // us, 11 / 15: @320 228.2 / 228.4, @160 73.7 / 71.6, 71.4 / 69.8, 71.4 / 70.8, 72.3 / 71.1 — and the
   // halo kernel keeps the @80 layers: 30.1 vs 32.2 / 34.1); of those two 4-wave forms the column-pair one
   // is the 4-wave choice, but the default is now the 8-wave form below.  YV7_WS64R=1: the ring form.
-  static const int ring = [] { const char* e = getenv("YV7_WS64R"); return e ? atoi(e) : 0; }();
+  static const int ring = env_int("YV7_WS64R", 0);
   // the 8-wave form (two waves per SIMD; variant 17) is the default since round 4: in-network, one layer
   // forced at a time (profiles/r4_ws8/, us, 4-wave -> 8-wave): yolov7 bs 32 @320 233.9 -> 218.2, the four
   // @160 layers 65.7-68.1 -> 61.6-63.5; w6 bs 8 @320 64.3-68.8 -> 62.0-63.0.  Variant 11 / YV7_WS64_4=1:
   // the 4-wave form.
-  static const int four = [] { const char* e = getenv("YV7_WS64_4"); return e ? atoi(e) : 0; }();   // A/B: 4-wave
-  if (p.variant == 17 || (p.variant != 11 && p.variant != 15 && !ring && !four)) {
-    if (p.act == 1) YV7_LAUNCH((conv3x3_ws64_kernel<1, 0, 8>), dim3(grid), dim3(512), 0, st, p);
-    else if (p.act == 2) YV7_LAUNCH((conv3x3_ws64_kernel<2, 0, 8>), dim3(grid), dim3(512), 0, st, p);
-    else YV7_LAUNCH((conv3x3_ws64_kernel<0, 0, 8>), dim3(grid), dim3(512), 0, st, p);
+  static const int four = env_int("YV7_WS64_4", 0);   // A/B: 4-wave
+  return launch_with_act(p.act, [&](auto A) {
+    constexpr int ACT = decltype(A)::value;
+    if (p.variant == 17 || (p.variant != 11 && p.variant != 15 && !ring && !four))
+      YV7_LAUNCH((conv3x3_ws64_kernel<ACT, 0, 8>), dim3(grid), dim3(512), 0, st, p);
+    else if (p.variant == 11 || (p.variant != 15 && !ring))
+      YV7_LAUNCH((conv3x3_ws64_kernel<ACT>), dim3(grid), dim3(NT), 0, st, p);
+    else
+      YV7_LAUNCH((conv3x3_ws64r_kernel<ACT>), dim3(grid), dim3(NT), 0, st, p);
     return hipGetLastError();
-  }
-  if (p.variant == 11 || (p.variant != 15 && !ring)) {
-    if (p.act == 1) YV7_LAUNCH((conv3x3_ws64_kernel<1>), dim3(grid), dim3(NT), 0, st, p);
-    else if (p.act == 2) YV7_LAUNCH((conv3x3_ws64_kernel<2>), dim3(grid), dim3(NT), 0, st, p);
-    else YV7_LAUNCH((conv3x3_ws64_kernel<0>), dim3(grid), dim3(NT), 0, st, p);
-    return hipGetLastError();
-  }
-  if (p.act == 1) YV7_LAUNCH((conv3x3_ws64r_kernel<1>), dim3(grid), dim3(NT), 0, st, p);
-  else if (p.act == 2) YV7_LAUNCH((conv3x3_ws64r_kernel<2>), dim3(grid), dim3(NT), 0, st, p);
-  else YV7_LAUNCH((conv3x3_ws64r_kernel<0>), dim3(grid), dim3(NT), 0, st, p);
-  return hipGetLastError();
+  });
 }
 
 }  // namespace yv7

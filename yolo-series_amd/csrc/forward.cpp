@@ -36,7 +36,7 @@ int launched(hipError_t e) { return e == hipSuccess ? 0 : hip_fail(e, "yv7_forwa
 // only; YV7_DUAL=0: off.  Fills the full-resolution conv *cf and its pooled partner *q; returns 2, or 0.
 int find_pair(const yv7_plan* p, size_t i, const Layout& l, unsigned char* wsb, yv7::ConvParams* cf,
               yv7::Conv1x1Pooled* q) {
-  static const int dual = [] { const char* ev = getenv("YV7_DUAL"); return ev ? atoi(ev) : 1; }();
+  static const int dual = yv7::env_int("YV7_DUAL", 1);
   if (!dual || p->dtype != YV7_DT_F16 || i + 1 >= p->ops.size() || p->op_variant[i] || p->op_variant[i + 1]) return 0;
   const auto& o = p->ops[i];
   const auto& o1 = p->ops[i + 1];
@@ -340,8 +340,8 @@ int forward_impl(yv7_plan* p, const void* x, int x_dtype, int B, int H, int W, f
 // YV7_CHAIN=1 chains every eligible stack.  Fills *c (pointers from workspace base wsb, null for a layout
 // query) and returns n (0: no chain here); the later ops of the chain record no time of their own.
 int yv7rt::find_chain(const yv7_plan* p, size_t i, const Layout& l, unsigned char* wsb, yv7::ChainParams* c) {
-  static const int all = [] { const char* e = getenv("YV7_CHAIN"); return e ? atoi(e) : 0; }();
-  static const long max_tasks = [] { const char* e = getenv("YV7_CHAIN_TASKS"); return e ? atol(e) : 1280L; }();
+  static const int all = yv7::env_int("YV7_CHAIN", 0);
+  static const long max_tasks = yv7::env_int("YV7_CHAIN_TASKS", 1280);
   if (p->dtype != YV7_DT_F16 || i >= p->ops.size()) return 0;
   const bool forced = p->op_variant[i] == 305;
   if (!forced && !all) return 0;
@@ -377,7 +377,7 @@ int yv7rt::find_chain(const yv7_plan* p, size_t i, const Layout& l, unsigned cha
       ok = bind_conv(p, i + j, l, wsb, &q);
       q.variant = 0;
       int cfg = yv7::lr_default_cfg(q);
-      if (cfg == 0 || cfg == 2) ++cfg;   // 128-channel tiles -> 64-channel (conv_lr.hip CHAIN_FORMS)
+      if (cfg == 0 || cfg == 2) ++cfg;   // 128-channel tiles -> 64-channel (conv_lr.hip chain_forms)
       if (cfg == 5 || cfg == 6) cfg = 1;  // 160-pixel tiles (H % 10 == 0) -> the 80-pixel 64-channel form
       if (cfg < 0 || (j > 1 && cfg != c->cfg1)) ok = false;
       if (j == 0) c->cfg0 = cfg;

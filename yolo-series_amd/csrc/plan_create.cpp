@@ -68,7 +68,7 @@ int validate_op(const yv7_net_desc* d, int i, size_t nbytes) {
 // packing, i.e. four kernel families, off at once).  Per fp16 plan: yolov7 54.0 MB (3x3 49.8 + 1x1 4.1) beside its 73.9 MB
 // blob, yolov7-w6 112.4 MB, yolov7-tiny 10.3 MB.
 bool wants_frag(int dtype, const yv7_op_desc& o) {
-  static const int lr = [] { const char* e = getenv("YV7_FRAG"); return e ? atoi(e) : 1; }();
+  static const int lr = yv7::env_int("YV7_FRAG", 1);
   const int nch = o.cin / 32;
   // the Detect head conv with K = 256 / 512 (conv_det_rw_kernel: the weights resident in VGPRs)
   if (dtype == YV7_DT_F16 && o.kind == YV7_OP_DETECT)

@@ -902,13 +902,7 @@ template <typename S, int ACT_A, int ACT_B>
 hipError_t stem_reorg_t(const StemParams& p, hipStream_t st) {
   const int HB = p.H / 4, WB = p.W / 4;
   const int ntiles = p.B * ((HB + 3) / 4) * ((WB + 15) / 16);
-  static const int cus = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) !=
-                                                 hipSuccess || v <= 0)
-      v = 256;
-    return v;
-  }();
+  const int cus = device_cus();
   const int nblk = ntiles < cus ? ntiles : cus;
   YV7_LAUNCH((stem_reorg_kernel<S, ACT_A, ACT_B>), dim3(nblk), dim3(NT_RG), 0, st, p);
   return hipGetLastError();
@@ -916,10 +910,8 @@ hipError_t stem_reorg_t(const StemParams& p, hipStream_t st) {
 
 template <typename S>
 hipError_t stem_reorg_acts(const StemParams& p, hipStream_t st) {
-  if (p.act_a == 1 && p.act_b == 1) return stem_reorg_t<S, 1, 1>(p, st);
-  if (p.act_a == 2 && p.act_b == 2) return stem_reorg_t<S, 2, 2>(p, st);
-  if (p.act_a == 0 && p.act_b == 0) return stem_reorg_t<S, 0, 0>(p, st);
-  return hipErrorInvalidValue;
+  if (p.act_a != p.act_b || p.act_a < 0 || p.act_a > 2) return hipErrorInvalidValue;
+  return launch_with_act(p.act_a, [&](auto A) { return stem_reorg_t<S, decltype(A)::value, decltype(A)::value>(p, st); });
 }
 
 template <typename S, int CA, int CB, int SA, int ACT_A, int ACT_B>
@@ -927,16 +919,10 @@ hipError_t stem_t(const StemParams& p, hipStream_t st) {
   constexpr int TBY = 8, TBX = 16;
   const int HB = p.H / SA / 2, WB = p.W / SA / 2;
   const int ntiles = p.B * ((HB + TBY - 1) / TBY) * ((WB + TBX - 1) / TBX);
-  static const int cus = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) !=
-                                                 hipSuccess || v <= 0)
-      v = 256;
-    return v;
-  }();
-  static const int occ = [] { const char* e = getenv("YV7_STEM_OCC"); return e ? atoi(e) : 2; }();
+  const int cus = device_cus();
+  static const int occ = env_int("YV7_STEM_OCC", 2);
   const int nblk = ntiles < cus * occ ? ntiles : cus * occ;   // persistent: blocks walk the tiles
-  static const int form = [] { const char* e = getenv("YV7_STEM"); return e ? atoi(e) : 2; }();
+  static const int form = env_int("YV7_STEM", 2);
   if constexpr (SA == 1) {   // (SA = 2, yolov7-tiny: its 10 patch pixels per thread leave stem2 one block per CU)
     if (form != 1) {
       YV7_LAUNCH((stem2_kernel<S, CA, CB, SA, TBY, TBX, ACT_A, ACT_B>), dim3(nblk), dim3(NT), 0, st, p);
@@ -949,10 +935,9 @@ hipError_t stem_t(const StemParams& p, hipStream_t st) {
 
 template <typename S, int CA, int CB, int SA>
 hipError_t stem_acts(const StemParams& p, hipStream_t st) {
-  if (p.act_a == 1 && p.act_b == 1) return stem_t<S, CA, CB, SA, 1, 1>(p, st);
-  if (p.act_a == 2 && p.act_b == 2) return stem_t<S, CA, CB, SA, 2, 2>(p, st);
-  if (p.act_a == 0 && p.act_b == 0) return stem_t<S, CA, CB, SA, 0, 0>(p, st);
-  return hipErrorInvalidValue;   // mixed activations: not a stem the graph compiler emits
+  // mixed activations: not a stem the graph compiler emits
+  if (p.act_a != p.act_b || p.act_a < 0 || p.act_a > 2) return hipErrorInvalidValue;
+  return launch_with_act(p.act_a, [&](auto A) { return stem_t<S, CA, CB, SA, decltype(A)::value, decltype(A)::value>(p, st); });
 }
 
 }  // namespace

@@ -4,7 +4,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cstdlib>
 #include <type_traits>
+#include <utility>
 
 namespace yv7 {
 
@@ -46,6 +48,37 @@ inline LaunchRec& launch_rec() {
                           __VA_ARGS__);                                                                    \
     if (ev_.stop) ev_.launches++;                                                                          \
   } while (0)
+
+int device_cus();   // CUs of the current device, 256 when the query fails (conv_f16.hip)
+
+// An integer switch from the environment (atol of the string; `dflt` when unset).  Callers keep it in a
+// function-local `static const`, so a switch is read once, on first use.
+inline long env_int(const char* name, long dflt) {
+  const char* e = getenv(name);
+  return e ? atol(e) : dflt;
+}
+
+// Calls f(std::integral_constant<int, ACT>) with the layer's activation as a compile-time constant: the
+// host side of with_act (below), for launchers whose kernel takes ACT as a template parameter.
+template <typename F>
+hipError_t launch_with_act(int act, F&& f) {
+  if (act == 1) return f(std::integral_constant<int, 1>{});
+  if (act == 2) return f(std::integral_constant<int, 2>{});
+  return f(std::integral_constant<int, 0>{});
+}
+
+// Calls f(std::integral_constant<int, row>) for 0 <= row < N: a table row as a compile-time constant.
+// A row outside the table is hipErrorInvalidValue.
+template <typename F, int... I>
+hipError_t launch_with_row_(int row, F&& f, std::integer_sequence<int, I...>) {
+  hipError_t e = hipErrorInvalidValue;
+  (void)((row == I && ((e = f(std::integral_constant<int, I>{})), true)) || ...);
+  return e;
+}
+template <int N, typename F>
+hipError_t launch_with_row(int row, F&& f) {
+  return launch_with_row_(row, static_cast<F&&>(f), std::make_integer_sequence<int, N>{});
+}
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef float f4 __attribute__((ext_vector_type(4)));
@@ -114,6 +147,19 @@ __host__ __device__ __forceinline__ size_t bordered_pixels(int B, int H, int W) 
 // Raw buffer resource over [base, base + bytes): loads at voffset >= bytes return zero.
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, uint32_t bytes) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, (int)bytes, 0x00020000);
+}
+constexpr uint32_t OOB = 0x80000000u;  // a buffer offset past every tensor: the load returns zeros
+
+// 16 bytes per lane from a buffer straight into LDS (lane-linear at the wave-uniform `lds` base)
+__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, void* lds, uint32_t vo, uint32_t so) {
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds, 16, vo, so, 0, 0);
+}
+
+// Counted wait: all but the N youngest vector-memory ops of the wave have landed.
+template <int N>
+__device__ __forceinline__ void vmwait() {
+  static_assert(N >= 0 && N < 64, "vmcnt range");
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
 // Kernel parameters of one conv launch (also the fused Detect head).
@@ -199,21 +245,27 @@ struct StemParams {
   int reorg;            // 1: the w6 front end (ReOrg + 12 -> 64 -> 128, wa k = tap*16 + ci), stem_reorg_kernel
 };
 
-// Host launchers (defined in the .hip files, called from the runtime).
+// Host launchers (defined in the .hip files, called from the runtime), by the file that defines them.
+// cfg arguments are rows of the file's configuration table.
+// conv.hip / conv_f16.hip: the dispatch
 hipError_t launch_conv(int dtype, const ConvParams& p, bool detect, hipStream_t st);
 bool det_writes_rowbest(int dtype);   // true when the head kernel launch_conv picks fills ConvParams::best
 hipError_t launch_conv_f16(const ConvParams& p, bool detect, hipStream_t st);
+// The low-resolution configuration the default fp16 dispatch gives a 3x3 stride-1 layer (conv_f16.hip
+// pick_tuned), or -1 when another kernel takes it.
+int lr_default_cfg(const ConvParams& p);
+// conv_halo.hip / conv_ws.hip / conv_hring.hip: the 16 x 16-pixel halo-tile 3x3 kernels
 bool halo_supported(const ConvParams& p);
+hipError_t launch_conv_halo(const ConvParams& p, hipStream_t st);
 bool ws64_supported(const ConvParams& p);
 hipError_t launch_conv_ws64(const ConvParams& p, hipStream_t st);
-hipError_t launch_conv_halo(const ConvParams& p, hipStream_t st);
 bool hring_supported(const ConvParams& p);
-// low-resolution 3x3 (conv_lr.hip): cfg 0-4 = tile shape; weights from ConvParams::wf
+hipError_t launch_conv_hring(const ConvParams& p, hipStream_t st);
+// conv_lr.hip: low-resolution 3x3, cfg = row of lr_rows; weights from ConvParams::wf
 bool lr_supported(const ConvParams& p, int cfg);
 hipError_t launch_conv_lr(const ConvParams& p, int cfg, hipStream_t st);
-// The low-resolution configuration the default fp16 dispatch gives a 3x3 stride-1 layer (conv_f16.hip
-// launch_conv_f16), or -1 when another kernel takes it.
-int lr_default_cfg(const ConvParams& p);
+size_t frag_bytes(int cin, int cout, int taps);
+hipError_t pack_frag(const void* w, int kpad, int cin, int cout, int taps, void* out, hipStream_t st);
 // A chain of 3x3 stride-1 convs at one resolution, each reading the previous one's output slice (an ELAN
 // block's 3x3 stack, cfg/deploy/yolov7.yaml:65-68, 84-87, 98-101, 113-116, 128-131) as ONE launch of
 // conv_lr.hip's tile body (conv3x3_chain_kernel): layer l + 1's tiles start as soon as the rows of layer l
@@ -225,21 +277,21 @@ struct ChainParams {
   int cfg0, cfg1;            // low-resolution configuration of layer 0 and of layers 1 .. nl - 1
   int* ctr;                  // chain_counter_bytes() of workspace scratch, zeroed once, re-armed by the kernel
 };
-// the chain's launch form exists (configurations, widths, activation) and its geometry is consistent;
+// the chain's launch form exists (a row of chain_forms, one activation) and its geometry is consistent;
 // ctr may be null here (a layout query)
 bool chain_supported(const ChainParams& c);
 size_t chain_counter_bytes(const ChainParams& c);
 long chain_tasks(const ChainParams& c);   // tiles of all layers
 hipError_t launch_conv_chain(const ChainParams& c, hipStream_t st);
-size_t frag_bytes(int cin, int cout, int taps);
-hipError_t pack_frag(const void* w, int kpad, int cin, int cout, int taps, void* out, hipStream_t st);
-hipError_t launch_conv_hring(const ConvParams& p, int cus, hipStream_t st);
-// stride-2 3x3 with the weights resident in VGPRs (conv_s2.hip): cfg 0-4 = tile shape; weights from wf
+// conv_s2.hip: stride-2 (and stride-1) 3x3 with the weights resident in VGPRs, cfg = row of s2_rows;
+// weights from wf
 bool s2_supported(const ConvParams& p, int cfg);
-hipError_t launch_conv_s2(const ConvParams& p, int cfg, int cus, hipStream_t st);
-// 1x1 with the weights resident in VGPRs (conv_w1.hip): cfg 0-5; weights from wf (1-tap fragment pack)
+hipError_t launch_conv_s2(const ConvParams& p, int cfg, hipStream_t st);
+// conv_w1.hip: 1x1 with the weights resident in VGPRs, cfg = row of w1_rows; weights from wf (1-tap
+// fragment pack)
 bool w1_supported(const ConvParams& p, int cfg);
-hipError_t launch_conv_w1(const ConvParams& p, int cfg, int cus, hipStream_t st);
+hipError_t launch_conv_w1(const ConvParams& p, int cfg, hipStream_t st);
+// elementwise.hip / stem.hip
 hipError_t launch_input(int dtype, const void* x, int x_dtype, void* y, int B, int H, int W, int yc,
                         bool reorg, hipStream_t st);
 hipError_t launch_maxpool(int dtype, const void* x, int B, int H, int W, int xc, int xoff, void* y, int Ho,
