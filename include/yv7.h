@@ -13,7 +13,8 @@
  *   yv7_forward       Model.forward / forward_once            models/yolo.py:581-631, including every
  *                     layer forward (Conv.fuseforward common.py:110-111, RepConv common.py:498-500,
  *                     SPPCSPC common.py:276-280, MP/SP common.py:30-45, ReOrg common.py:48-53,
- *                     Concat common.py:56-62, nn.Upsample) and Detect/IDetect decode yolo.py:42-63,140-160
+ *                     Concat common.py:56-62, Shortcut common.py:80-86, DownC common.py:181-192, nn.Upsample)
+ *                     and Detect/IDetect decode yolo.py:42-63,140-160
  *   yv7_nms           non_max_suppression()                   utils/general.py:628-720 incl. the
  *                     torchvision.ops.nms call at general.py:704
  *   yv7_end2end       TRT EfficientNMS_TRT plugin contract    models/experimental.py:111-156,
@@ -31,7 +32,7 @@
 extern "C" {
 #endif
 
-#define YV7_ABI_VERSION 4
+#define YV7_ABI_VERSION 5
 
 /* Activation tensors in the forward workspace are NHWC with a YV7_BORDER-pixel zero frame around
  * every image: [B][h + 2*YV7_BORDER][w + 2*YV7_BORDER][C].  Kernels write only interiors; the frame
@@ -66,9 +67,11 @@ typedef enum {
   YV7_OP_UPSAMPLE = 3, /* nearest-neighbour x2 */
   YV7_OP_COPY = 4,     /* channel-slice copy (concat input that could not be written in place) */
   YV7_OP_DETECT = 5,   /* 1x1 conv + bias + sigmoid + grid/anchor decode -> z rows, raw logits */
-  YV7_OP_STEM = 6      /* fp16: image -> conv A (3->32, 3x3, stride s) -> conv B (32->64, 3x3, s2), A kept in LDS;
+  YV7_OP_STEM = 6,     /* fp16: image -> conv A (3->32, 3x3, stride s) -> conv B (32->64, 3x3, s2), A kept in LDS;
                           cin 12: the yolov7-w6 front end, image -> ReOrg (common.py:48-53) -> conv A (12->64,
                           3x3, s1; weights K = tap*16 + ci) -> conv B (64->128, 3x3, s2) */
+  YV7_OP_ADD = 7       /* dst = src + src2 over cout channels (Shortcut, common.py:80-86): three channel slices with
+                          their own tensors, offsets and pitches; fp16 adds in fp32 and rounds once */
 } yv7_op_kind;
 
 /* One NHWC activation tensor of the plan: [B, H >> shift, W >> shift, channels]. Tensor 0 is the
@@ -94,6 +97,10 @@ typedef struct {
   int32_t pool;                /* CONV (fp16 plans, 1x1): 2 = the input is first max-pooled 2x2 / stride 2 (an MP
                                   layer, common.py:30-36, folded into the conv's operand loads); then s = 2 */
   int32_t reserved;
+  int32_t src2, src2_coff;     /* ADD: the second operand's tensor and channel offset (cout channels).  CONV (fp16
+                                  plans, wfmt PLAN, pool 0): a residual of the output's resolution, cout channels at
+                                  src2_coff, added after bias and activation in fp32 and rounded once (a Shortcut
+                                  folded into its producer); -1 = none.  Every other kind: -1 */
 } yv7_op_desc;
 
 typedef struct {
@@ -153,7 +160,9 @@ int yv7_forward(yv7_plan* plan, const void* x, int x_dtype, int B, int H, int W,
  * buf receives a NUL-terminated string. */
 int yv7_op_kernels(yv7_plan* plan, int B, int H, int W, int x_dtype, char* buf, size_t bytes);
 
-/* Force the kernel configuration of one CONV / DETECT op (0 = the tuned dispatch, the default).  For
+/* Force the kernel configuration of one CONV / DETECT op (0 = the tuned dispatch, the default).  A CONV that
+ * carries a residual takes only the variants of the families with the residual epilogue (1, 4, 6 and the ring's
+ * 100 + 10 * configuration + K splits); any other is an error.  For
  * parity tests of every kernel variant and A/B timing; the accepted values are the real kernel
  * configurations of the fp16 dispatch (the `abi` rows of csrc/conv_f16.hip's forced-variant table),
  * never its microbenchmark hooks.  A split-K

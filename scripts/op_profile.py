@@ -9,11 +9,12 @@ from yv7.synthetic import synthetic_state_dict
 from yv7 import _lib as L
 ap = argparse.ArgumentParser(); ap.add_argument('--model', default='yolov7'); ap.add_argument('--b', type=int, default=32)
 ap.add_argument('--img', type=int, default=640); ap.add_argument('--dtype', default='f16'); ap.add_argument('--iters', type=int, default=10)
+ap.add_argument('--calib', type=int, default=0, help='calibration frame size of the synthetic weights (0: the native size)')
 ap.add_argument('--csv', default=''); ap.add_argument('--top', type=int, default=40)
 ap.add_argument('--dump', default='', help='JSON of every op: desc, kernels, us, algorithmic bytes (scripts/pmc_ops.py)')
 a = ap.parse_args()
 dt = torch.float32 if a.dtype == 'f32' else torch.float16
-m = Model(a.model); synthetic_state_dict(m, seed=0); m = m.float().fuse().eval()
+m = Model(a.model); synthetic_state_dict(m, seed=0, calib_hw=a.calib or None); m = m.float().fuse().eval()
 plan = Plan.from_model(m, 'cuda:0', 'fp8' if a.dtype == 'fp8' else dt)
 B, H = a.b, a.img
 x = torch.rand(B, 3, H, H, device='cuda:0').to(dt)
@@ -25,7 +26,7 @@ for _ in range(a.iters): plan.forward_into(x, z)
 torch.cuda.synchronize()
 n, ms = plan.profile_read()
 costs = plan.op_costs(B, H, H, x_bytes=x.element_size(), with_raw=False)
-names = {0: 'INPUT', 1: 'CONV', 2: 'POOL', 3: 'UPS', 4: 'COPY', 5: 'DET', 6: 'STEM'}
+names = {0: 'INPUT', 1: 'CONV', 2: 'POOL', 3: 'UPS', 4: 'COPY', 5: 'DET', 6: 'STEM', 7: 'ADD'}
 tot = sum(ms) / n
 # An op without a kernel of its own (the second op of the dual 1x1 launch, the later pools of the SPPCSPC
 # cascade) runs inside the launch of the op before it: its bytes, FLOPs and (zero-length) event time are

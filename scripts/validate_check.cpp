@@ -23,6 +23,7 @@ static yv7_op_desc op(int kind) {
   std::memset(&o, 0, sizeof(o));
   o.kind = kind;
   o.k = o.s = 1;
+  o.src2 = -1;   // no second operand
   return o;
 }
 
@@ -78,6 +79,35 @@ int main() {
     m.src = m.dst = 1, m.dst_coff = 8, m.cout = 16;
     n.ops.insert(n.ops.begin() + 2, m);
   });
+  // ADD (t1 + t2 -> t3, 16 channels each) and the second-operand field of the other kinds
+  auto with_add = [](Net& n) {
+    n.t = {{8, 0}, {16, 0}, {16, 0}, {16, 0}};
+    yv7_op_desc a = op(YV7_OP_ADD);
+    a.src = 1, a.src2 = 2, a.dst = 3, a.cout = 16;
+    n.ops.insert(n.ops.begin() + 2, a);
+  };
+  bad += check(nullptr, with_add);
+  bad += check("op 2 bad second-operand tensor id", [&](Net& n) { with_add(n), n.ops[2].src2 = 9; });
+  bad += check("op 2 add channels not a multiple of the vector", [&](Net& n) { with_add(n), n.ops[2].cout = 12; });
+  bad += check("op 2 second-operand channel slice out of range", [&](Net& n) { with_add(n), n.ops[2].src2_coff = 8; });
+  bad += check("op 2 add operands and result differ in resolution", [&](Net& n) {
+    with_add(n), n.t[2].shift = 1, n.d.max_shift = 1;
+  });
+  bad += check("op 2 add result overlaps an operand", [&](Net& n) { with_add(n), n.ops[2].dst = 2; });
+  // a residual on the conv (op 1: t0 -> t1, 16 channels), from a third tensor t2
+  auto with_res = [](Net& n) {
+    n.t = {{8, 0}, {16, 0}, {16, 0}};
+    n.ops[1].src2 = 2;
+  };
+  bad += check(nullptr, with_res);
+  bad += check("op 1 residual overlaps the result", [](Net& n) { n.ops[1].src2 = 1; });
+  bad += check("op 1 residual needs an fp16 plan", [&](Net& n) { with_res(n), n.ops[1].pool = 2; });
+  bad += check("op 1 residual needs an fp16 plan", [&](Net& n) { with_res(n), n.ops[1].wfmt = YV7_WFMT_FP8, n.ops[1].xscale = 1.f; });
+  bad += check("op 1 residual needs an fp16 plan", [&](Net& n) { with_res(n), n.d.dtype = YV7_DT_F32; });
+  bad += check("op 1 bad residual tensor id", [&](Net& n) { with_res(n), n.ops[1].src2 = 9; });
+  bad += check("op 1 residual channel slice out of range", [&](Net& n) { with_res(n), n.ops[1].src2_coff = 8; });
+  bad += check("op 1 residual and result differ in resolution", [&](Net& n) { with_res(n), n.t[2].shift = 1, n.d.max_shift = 1; });
+  bad += check("op 2 takes no second operand", [](Net& n) { n.ops[2].src2 = 0; });
   std::printf("%d failed\n", bad);
   return bad ? 1 : 0;
 }

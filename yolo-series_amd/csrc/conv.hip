@@ -269,6 +269,8 @@ hipError_t launch_conv(int dtype, const ConvParams& p, bool detect, hipStream_t 
   // (YV7_CONV_V1=1 selects this file's generic kernel, for A/B)
   const bool v1 = use_v1();
   if (p.pool) return dtype == 1 ? launch_conv_f16(p, detect, st) : hipErrorInvalidValue;   // MP-folded 1x1
+  // a residual operand: only conv_f16.hip's tile / ring kernels add it (there variant 1 is the register-staged tile)
+  if (p.res) return dtype == 1 ? launch_conv_f16(p, detect, st) : hipErrorInvalidValue;
   // cout <= 32 (the stem of every model, tiny's narrow layers): this kernel's BK=32 steps waste less
   // of the short, padded K than the 64-deep steps of conv_f16 (measured: scripts/convbench.hip)
   if (dtype == 1)

@@ -465,8 +465,34 @@ Pick pick_tuned(const ConvParams& p) {
   return pick_tile(p);
 }
 
+// A conv that carries a residual (ConvParams::res): only the two families whose epilogue adds it, the
+// register-staged tile kernel and the 8-wave ring (conv_f16_ring.hip).  Tuned: the ring rule where it applies,
+// the wide rings while their grid covers the chip, else the 128 x 128 ring; up to 32 outputs the tile kernel.  A
+// forced variant of another family (yv7_set_op_variant refuses it; YV7_CONV_F16 can still name one) runs the
+// tile kernel, as a forced form that does not apply does.  The pooled and Detect paths refuse a residual.
+Pick pick_res(const ConvParams& p, bool det, int variant) {
+  if (det || p.pool) return {F_INVALID};
+  Pick k;
+  if (variant) {
+    k = pick_forced(p, variant);
+  } else if (p.cout <= 32) {
+    k = pick_tile(p);
+  } else if (const Choice ch = choose(p, 0); ch.cfg >= 0) {
+    k = {F_RING, ch.cfg, ch.S};
+  } else {
+    const long mt = (p.M + 255) / 256;
+    k = {F_RING, p.cout >= 256 && mt * ((p.cout + 255) / 256) >= 150   ? R256x256
+                 : p.cout >= 256 && mt * ((p.cout + 127) / 128) >= 150 ? R256x128
+                                                                        : R128x128s2};
+  }
+  if (k.fam == F_RING && k.cfg < NCFG) return {F_RING, RRES + k.cfg, k.S};
+  const Pick t = pick_tile(p);   // (also a ring row without a residual form: the narrow-layer rows of 5 and 7)
+  return {F_TILE, t.cfg == T128x32 ? T128x32res : t.cfg == T128x64 ? T128x64res : T128x128res};
+}
+
 Pick pick(const ConvParams& p, bool det) {
   const int variant = p.variant ? p.variant : env_variant();
+  if (p.res) return pick_res(p, det, variant);
   if (p.pool) return pick_pool(p, det);
   if (det) return pick_det(p, variant);
   return variant ? pick_forced(p, variant) : pick_tuned(p);
@@ -496,6 +522,10 @@ bool conv_f16_variant_is_config(int v) {
   for (const Forced& f : forced_rows)
     if (v >= f.first && v <= f.last) return f.abi && (v < 100 || f.fam != F_RING || v % 10 <= 4);
   return false;
+}
+
+bool conv_f16_variant_has_residual(int v) {
+  return v == 1 || v == 4 || v == 6 || (v >= 100 && v < 100 + 10 * NCFG && v % 10 <= 4);
 }
 
 hipError_t launch_conv_f16(const ConvParams& p, bool det, hipStream_t st) { return launch_pick(p, pick(p, det), st); }

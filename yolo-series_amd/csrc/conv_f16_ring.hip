@@ -1,7 +1,7 @@
 // The two non-persistent main loops of the fp16 implicit-GEMM conv (conv_f16.hip describes the GEMM
 // view): the 4-wave register-staged tile kernel (2-3 blocks per CU, any width; also the MP-folded 1x1)
 // and the 8-wave LDS-DMA ring for wide layers, with its split-K hand-off.  Both have a DET form that
-// ends in the fused Detect epilogue (conv_det.h).
+// ends in the fused Detect epilogue (conv_det.h) and a RES form whose epilogue adds a residual operand.
 #include "conv_det.h"
 #include "conv_f16_launch.h"
 
@@ -18,8 +18,32 @@ __device__ __forceinline__ u4 hmax4(u4 a, u4 b, u4 c, u4 d) {
 
 // POOL: 1x1 conv over the 2x2 / stride-2 max of the input (ConvParams::pool; k = 1, s = 2, pad = 0): each A
 // row's origin is the window's top-left pixel, the other three are fixed byte offsets.
-template <int BM, int BN, int WM, bool ONE, bool DET, int PF = 1, bool POOL = false>
-__global__ __launch_bounds__(NT, 2) void conv_f16_kernel(const ConvParams p) {
+// RES: the residual epilogue (a Shortcut, models/common.py:80-86, folded into the conv that produces one of its
+// operands): after bias and activation in fp32 the fp16 residual at the same (pixel, channel) is added and the sum
+// rounded once.  Each lane fetches the four channels of its accumulator fragments as 8-byte buffer loads from the
+// residual slice (pitch rc, offset roff, the output's geometry); rows past M and channels past cout take the
+// out-of-range offset and read nothing.  The loads follow the K loop, ahead of the epilogue's LDS staging — not
+// behind the tile's stores.  A compile-time flag of the shared body: the kernels without it are the code they were.
+template <int TM>
+__device__ __forceinline__ void res_rows(const ConvParams& p, int m_first, uint32_t (&ro)[TM]) {
+#pragma unroll
+  for (int i = 0; i < TM; ++i) {
+    const int m = m_first + i * 16;
+    ro[i] = OOB;
+    if (m < p.M) {
+      PixelWalk pw(p, m);
+      ro[i] = (uint32_t)((pix_index(pw.b, pw.ho, pw.wo, p.Ho, p.Wo) * p.rc + p.roff) * 2);
+    }
+  }
+}
+typedef _Float16 h4r __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ h4r res_load(__amdgpu_buffer_rsrc_t rr, uint32_t row, int n, int cout) {
+  const uint32_t vo = (row != OOB && n < cout) ? row + (uint32_t)n * 2 : OOB;
+  return __builtin_bit_cast(h4r, __builtin_amdgcn_raw_buffer_load_b64(rr, vo, 0, 0));
+}
+
+template <int BM, int BN, int WM, bool ONE, bool DET, int PF, bool POOL, bool RES>
+__device__ __forceinline__ void conv_f16_body(const ConvParams& p) {
   constexpr int WN = 4 / WM;
   constexpr int WTM = BM / WM, WTN = BN / WN;
   constexpr int TM = WTM / 16, TN = WTN / 16;
@@ -182,18 +206,31 @@ __global__ __launch_bounds__(NT, 2) void conv_f16_kernel(const ConvParams p) {
     yrow[tid] = v;
   }
   unsigned char* Cs = smem;
+  [[maybe_unused]] uint32_t rrow[TM];
+  [[maybe_unused]] const auto rr = make_rsrc(RES ? p.res : p.zero, RES ? p.rbytes : 0u);
+  if constexpr (RES) res_rows<TM>(p, m0 + wm * WTM + li, rrow);
   with_act(p.act, [&](auto actc) {
     constexpr int ACT = decltype(actc)::value;
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
       const int col = wn * WTN + j * 16 + g * 4;
+      [[maybe_unused]] h4r rv[TM];
+      if constexpr (RES) {
+#pragma unroll
+        for (int i = 0; i < TM; ++i) rv[i] = res_load(rr, rrow[i], n0 + col, p.cout);
+      }
 #pragma unroll
       for (int i = 0; i < TM; ++i) {
         const int row = wm * WTM + i * 16 + li;
         typedef _Float16 h4 __attribute__((ext_vector_type(4)));
         h4 v;
+        if constexpr (RES) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = (_Float16)act_t<ACT>(acc[j][i][e]);
+          for (int e = 0; e < 4; ++e) v[e] = (_Float16)(act_t<ACT>(acc[j][i][e]) + (float)rv[i][e]);
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = (_Float16)act_t<ACT>(acc[j][i][e]);
+        }
         *reinterpret_cast<h4*>(Cs + row * CPITCH + col * 2) = v;
       }
     }
@@ -284,8 +321,8 @@ __device__ __forceinline__ bool splitk_reduce(const ConvParams& p, unsigned char
 //  * counted `s_waitcnt vmcnt(PER)` keeps the next stage in flight across a raw s_barrier (never
 //    __syncthreads in the loop: its fence would drain the DMA); the stage refilled at step kt is the
 //    one every wave finished reading at step kt-1 (its MFMAs consumed those reads before the barrier).
-template <int BM, int BN, int WM, int WN, int STAGES, bool ONE, bool DET = false>
-__global__ __launch_bounds__(64 * WM * WN, (STAGES * (BM + BN) * 128 <= 80 * 1024) ? 2 : 1) void conv_f16_ring_kernel(const ConvParams p) {
+template <int BM, int BN, int WM, int WN, int STAGES, bool ONE, bool DET, bool RES>
+__device__ __forceinline__ void conv_f16_ring_body(const ConvParams& p) {
   constexpr int NW = WM * WN, NTH = 64 * NW;
   constexpr int WTM = BM / WM, WTN = BN / WN;
   constexpr int TM = WTM / 16, TN = WTN / 16;
@@ -419,18 +456,31 @@ __global__ __launch_bounds__(64 * WM * WN, (STAGES * (BM + BN) * 128 <= 80 * 102
     yrow[t] = v;
   }
   unsigned char* Cs = smem;
+  [[maybe_unused]] uint32_t rrow[TM];
+  [[maybe_unused]] const auto rr = make_rsrc(RES ? p.res : p.zero, RES ? p.rbytes : 0u);
+  if constexpr (RES) res_rows<TM>(p, m0 + wm * WTM + li, rrow);
   with_act(p.act, [&](auto actc) {
     constexpr int ACT = decltype(actc)::value;
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
       const int col = wn * WTN + j * 16 + g * 4;
+      [[maybe_unused]] h4r rv[TM];
+      if constexpr (RES) {
+#pragma unroll
+        for (int i = 0; i < TM; ++i) rv[i] = res_load(rr, rrow[i], n0 + col, p.cout);
+      }
 #pragma unroll
       for (int i = 0; i < TM; ++i) {
         const int row = wm * WTM + i * 16 + li;
         typedef _Float16 h4 __attribute__((ext_vector_type(4)));
         h4 v;
+        if constexpr (RES) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = (_Float16)act_t<ACT>(acc[j][i][e]);
+          for (int e = 0; e < 4; ++e) v[e] = (_Float16)(act_t<ACT>(acc[j][i][e]) + (float)rv[i][e]);
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = (_Float16)act_t<ACT>(acc[j][i][e]);
+        }
         *reinterpret_cast<h4*>(Cs + row * CPITCH + col * 2) = v;
       }
     }
@@ -447,14 +497,38 @@ __global__ __launch_bounds__(64 * WM * WN, (STAGES * (BM + BN) * 128 <= 80 * 102
   }
 }
 
-template <int BM, int BN, int WM, bool ONE, bool DET, int PF, bool POOL>
+template <int BM, int BN, int WM, bool ONE, bool DET, int PF = 1, bool POOL = false>
+__global__ __launch_bounds__(NT, 2) void conv_f16_kernel(const ConvParams p) {
+  conv_f16_body<BM, BN, WM, ONE, DET, PF, POOL, false>(p);
+}
+template <int BM, int BN, int WM, bool ONE>
+__global__ __launch_bounds__(NT, 2) void conv_f16_res_kernel(const ConvParams p) {
+  conv_f16_body<BM, BN, WM, ONE, false, 1, false, true>(p);
+}
+template <int BM, int BN, int WM, int WN, int STAGES, bool ONE, bool DET = false>
+__global__ __launch_bounds__(64 * WM * WN, (STAGES * (BM + BN) * 128 <= 80 * 1024) ? 2 : 1) void conv_f16_ring_kernel(const ConvParams p) {
+  conv_f16_ring_body<BM, BN, WM, WN, STAGES, ONE, DET, false>(p);
+}
+template <int BM, int BN, int WM, int WN, int STAGES, bool ONE>
+__global__ __launch_bounds__(64 * WM * WN, (STAGES * (BM + BN) * 128 <= 80 * 1024) ? 2 : 1) void conv_f16_ring_res_kernel(const ConvParams p) {
+  conv_f16_ring_body<BM, BN, WM, WN, STAGES, ONE, false, true>(p);
+}
+
+template <int BM, int BN, int WM, bool ONE, bool DET, int PF, bool POOL, bool RES>
 hipError_t launch_t(const ConvParams& p, hipStream_t st) {
   const int nM = (p.M + BM - 1) / BM, nN = (p.cout + BN - 1) / BN;
-  YV7_LAUNCH((conv_f16_kernel<BM, BN, WM, ONE, DET, PF, POOL>), dim3(nM * nN), dim3(NT), 0, st, p);
+  if constexpr (RES) {
+    static_assert(!DET && !POOL && PF == 1, "the residual rows are plain tiles");
+    if (!p.res) return hipErrorInvalidValue;
+    YV7_LAUNCH((conv_f16_res_kernel<BM, BN, WM, ONE>), dim3(nM * nN), dim3(NT), 0, st, p);
+  } else {
+    if (p.res) return hipErrorInvalidValue;   // a row without the residual epilogue would drop the operand
+    YV7_LAUNCH((conv_f16_kernel<BM, BN, WM, ONE, DET, PF, POOL>), dim3(nM * nN), dim3(NT), 0, st, p);
+  }
   return hipGetLastError();
 }
 
-template <int BM, int BN, int WM, int WN, int STAGES, bool ONE, bool DET>
+template <int BM, int BN, int WM, int WN, int STAGES, bool ONE, bool DET, bool RES>
 hipError_t launch_r(const ConvParams& p0, int S, hipStream_t st) {
   ConvParams p = p0;
   const long tiles = (long)((p.M + BM - 1) / BM) * ((p.cout + BN - 1) / BN);
@@ -465,7 +539,14 @@ hipError_t launch_r(const ConvParams& p0, int S, hipStream_t st) {
       return hipErrorInvalidValue;   // the caller sized the scratch with conv_splitk_part_bytes
     nblk = (unsigned)(tiles * S);
   }
-  YV7_LAUNCH((conv_f16_ring_kernel<BM, BN, WM, WN, STAGES, ONE, DET>), dim3(nblk), dim3(64 * WM * WN), 0, st, p);
+  if constexpr (RES) {
+    static_assert(!DET, "the residual rows are plain rings");
+    if (!p.res) return hipErrorInvalidValue;
+    YV7_LAUNCH((conv_f16_ring_res_kernel<BM, BN, WM, WN, STAGES, ONE>), dim3(nblk), dim3(64 * WM * WN), 0, st, p);
+  } else {
+    if (p.res) return hipErrorInvalidValue;
+    YV7_LAUNCH((conv_f16_ring_kernel<BM, BN, WM, WN, STAGES, ONE, DET>), dim3(nblk), dim3(64 * WM * WN), 0, st, p);
+  }
   return hipGetLastError();
 }
 
@@ -475,9 +556,9 @@ hipError_t launch_tile(const ConvParams& p, int row, hipStream_t st) {
   const bool one = p.k == 1 && p.s == 1 && p.pad == 0;
   return launch_with_row<NTILE>(row, [&](auto I) {
     constexpr TileRow r = tile_rows[decltype(I)::value];
-    if constexpr (r.one != ONE_BOTH) return launch_t<r.bm, r.bn, r.wm, r.one == ONE_ONLY, r.det, r.pf, r.pool>(p, st);
-    else return one ? launch_t<r.bm, r.bn, r.wm, true, r.det, r.pf, r.pool>(p, st)
-                    : launch_t<r.bm, r.bn, r.wm, false, r.det, r.pf, r.pool>(p, st);
+    if constexpr (r.one != ONE_BOTH) return launch_t<r.bm, r.bn, r.wm, r.one == ONE_ONLY, r.det, r.pf, r.pool, r.res>(p, st);
+    else return one ? launch_t<r.bm, r.bn, r.wm, true, r.det, r.pf, r.pool, r.res>(p, st)
+                    : launch_t<r.bm, r.bn, r.wm, false, r.det, r.pf, r.pool, r.res>(p, st);
   });
 }
 
@@ -485,9 +566,9 @@ hipError_t launch_ring(const ConvParams& p, int row, int S, hipStream_t st) {
   const bool one = p.k == 1 && p.s == 1 && p.pad == 0;
   return launch_with_row<NRING>(row, [&](auto I) {
     constexpr RingRow r = ring_rows[decltype(I)::value];
-    if constexpr (r.one != ONE_BOTH) return launch_r<r.bm, r.bn, r.wm, r.wn, r.stages, r.one == ONE_ONLY, r.det>(p, S, st);
-    else return one ? launch_r<r.bm, r.bn, r.wm, r.wn, r.stages, true, r.det>(p, S, st)
-                    : launch_r<r.bm, r.bn, r.wm, r.wn, r.stages, false, r.det>(p, S, st);
+    if constexpr (r.one != ONE_BOTH) return launch_r<r.bm, r.bn, r.wm, r.wn, r.stages, r.one == ONE_ONLY, r.det, r.res>(p, S, st);
+    else return one ? launch_r<r.bm, r.bn, r.wm, r.wn, r.stages, true, r.det, r.res>(p, S, st)
+                    : launch_r<r.bm, r.bn, r.wm, r.wn, r.stages, false, r.det, r.res>(p, S, st);
   });
 }
 

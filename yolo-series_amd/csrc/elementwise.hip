@@ -1,10 +1,10 @@
 // Byte-moving kernels of the yv7 path (gfx950): input packing (+ fused ReOrg), max pooling,
-// nearest x2 upsample and channel-slice copy.  All NHWC, 16-byte vectors per lane, grid-stride.
+// nearest x2 upsample, channel-slice copy and the residual add.  All NHWC, 16-byte vectors per lane, grid-stride.
 //
 // Replaces: detect.py:100-104 (the [0,1] float image batch handed to the model, here packed NCHW ->
 // NHWC), ReOrg models/common.py:48-53 (fused into the packing), MP common.py:30-36, SP common.py:39-45,
 // SPPCSPC's MaxPool2d(k, 1, k//2) common.py:271, nn.Upsample(None, 2, 'nearest') and the
-// Concat copies common.py:56-62 that zero-copy slice writes could not absorb.
+// Concat copies common.py:56-62 that zero-copy slice writes could not absorb, Shortcut common.py:80-86.
 #include "yv7_kernels.h"
 
 namespace yv7 {
@@ -124,6 +124,55 @@ __global__ __launch_bounds__(NT) void copy_kernel(const T* __restrict__ x, int B
     const int b = t / H, h = t - b * H;
     const size_t q = pix_index(b, h, w, H, W);
     *reinterpret_cast<u4*>(y + q * yc + yoff + c) = *reinterpret_cast<const u4*>(x + q * xc + xoff + c);
+  }
+}
+
+// ---- Shortcut (common.py:80-86): y = a + b over channel slices of three tensors, each with its own pitch and
+//      offset.  Pure streaming, no reuse inside the kernel: every lane keeps ADD_U (a, b) vector pairs — 2 * ADD_U
+//      16-byte loads — in flight before the first add, the items of one lane a whole grid apart so that each of
+//      the ADD_U rounds stays coalesced.  fp16 adds in fp32 and rounds once, to nearest even.  NTS: nontemporal
+//      stores (the sum is never re-read by this kernel; whether the next op finds it in cache is what the A/B in
+//      DESIGN.md §4 measures).
+constexpr int ADD_U = 4;
+
+template <typename T, bool NTS>
+__global__ __launch_bounds__(NT) void add_kernel(const T* a, int ac, int aoff, const T* b,
+                                                 int bc, int boff, T* __restrict__ y, int yc, int yoff, int B, int H,
+                                                 int W, int C) {
+  constexpr int V = Vec<T>::N;
+  const int cv = C / V;
+  const int total = B * H * W * cv;
+  const int step = gridDim.x * NT;
+  for (int i0 = blockIdx.x * NT + threadIdx.x; i0 < total; i0 += ADD_U * step) {
+    u4 va[ADD_U], vb[ADD_U];
+    size_t q[ADD_U];
+    int c[ADD_U];
+#pragma unroll
+    for (int u = 0; u < ADD_U; ++u) {
+      const int i = i0 + u * step;
+      if (i < total) {
+        const int pix = i / cv;
+        c[u] = (i - pix * cv) * V;
+        const int t = pix / W, w = pix - t * W;
+        const int bb = t / H, h = t - bb * H;
+        q[u] = pix_index(bb, h, w, H, W);
+        va[u] = *reinterpret_cast<const u4*>(a + q[u] * ac + aoff + c[u]);
+        vb[u] = *reinterpret_cast<const u4*>(b + q[u] * bc + boff + c[u]);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < ADD_U; ++u) {
+      if (i0 + u * step < total) {
+        const T* ea = reinterpret_cast<const T*>(&va[u]);
+        const T* eb = reinterpret_cast<const T*>(&vb[u]);
+        alignas(16) T r[V];
+#pragma unroll
+        for (int e = 0; e < V; ++e) r[e] = (T)((float)ea[e] + (float)eb[e]);
+        u4* out = reinterpret_cast<u4*>(y + q[u] * yc + yoff + c[u]);
+        if constexpr (NTS) __builtin_nontemporal_store(*reinterpret_cast<const u4*>(r), out);
+        else *out = *reinterpret_cast<const u4*>(r);
+      }
+    }
   }
 }
 
@@ -293,6 +342,29 @@ hipError_t launch_copy(int dtype, const void* x, int B, int H, int W, int xc, in
   else
     YV7_LAUNCH(copy_kernel<float>, dim3(grid_for(work)), dim3(NT), 0, st, (const float*)x, B, H, W, xc, xoff,
                        (float*)y, yc, yoff, C);
+  return hipGetLastError();
+}
+
+hipError_t launch_add(int dtype, const void* a, int ac, int aoff, const void* b, int bc, int boff, void* y, int yc,
+                      int yoff, int B, int H, int W, int C, hipStream_t st) {
+  static const int nts = env_int("YV7_ADD_NT", 0);
+  const int V = dtype == 1 ? 8 : 4;
+  const size_t work = (size_t)B * H * W * (C / V);
+  // 32-bit item indices (see above), a lane's last round included
+  if (C <= 0 || C % V || work + (size_t)ADD_U * 256 * 16 * NT >= ((size_t)1 << 31)) return hipErrorInvalidValue;
+  const dim3 grid(grid_for((work + ADD_U - 1) / ADD_U));
+  auto go = [&](auto t, auto n) {
+    using T = decltype(t);
+    YV7_LAUNCH((add_kernel<T, decltype(n)::value>), grid, dim3(NT), 0, st, (const T*)a, ac, aoff, (const T*)b, bc, boff,
+               (T*)y, yc, yoff, B, H, W, C);
+  };
+  if (dtype == 1) {
+    if (nts) go(_Float16{}, std::true_type{});
+    else go(_Float16{}, std::false_type{});
+  } else {
+    if (nts) go(float{}, std::true_type{});
+    else go(float{}, std::false_type{});
+  }
   return hipGetLastError();
 }
 

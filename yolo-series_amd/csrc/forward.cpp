@@ -43,7 +43,7 @@ int find_pair(const yv7_plan* p, size_t i, const Layout& l, unsigned char* wsb, 
   // one launch reads the shared slice while it writes both outputs: neither output may overlap the input
   // slice or the other output (in order, op i + 1 would see op i's writes) — the hazards graph.py's
   // _merge_siblings checks before its fusions
-  if (o1.kind != YV7_OP_CONV || is_f8(o1) || o1.src != o.src || o1.src_coff != o.src_coff || o1.cin != o.cin ||
+  if (o1.kind != YV7_OP_CONV || is_f8(o1) || o.src2 >= 0 || o1.src2 >= 0 || o1.src != o.src || o1.src_coff != o.src_coff || o1.cin != o.cin ||
       o1.k != 1 || o.k != 1 || (o.pool == 2) == (o1.pool == 2) || o1.w_off == o.w_off ||
       overlap(o.dst, o.dst_coff, o.cout, o.src, o.src_coff, o.cin) ||
       overlap(o1.dst, o1.dst_coff, o1.cout, o.src, o.src_coff, o.cin) ||
@@ -231,6 +231,15 @@ int op_copy(const Fwd& f, const yv7_op_desc& o) {
                                    o.src_coff, f.at(o.dst), to.channels, o.dst_coff, o.cout, f.st));
 }
 
+int op_add(const Fwd& f, const yv7_op_desc& o) {
+  const auto& ta = f.p->tensors[o.src];
+  const auto& tb = f.p->tensors[o.src2];
+  const auto& to = f.p->tensors[o.dst];
+  return launched(yv7::launch_add(f.p->dtype, f.at(o.src), ta.channels, o.src_coff, f.at(o.src2), tb.channels,
+                                  o.src2_coff, f.at(o.dst), to.channels, o.dst_coff, f.l.B, f.l.H >> to.shift,
+                                  f.l.W >> to.shift, o.cout, f.st));
+}
+
 // Launches op i, or the fused group that starts at it: *n ops (1 unless a recogniser found a group).
 int run_op(const Fwd& f, size_t i, size_t* n) {
   const yv7_op_desc& o = f.p->ops[i];
@@ -242,6 +251,7 @@ int run_op(const Fwd& f, size_t i, size_t* n) {
     case YV7_OP_MAXPOOL: return op_maxpool(f, i, n);
     case YV7_OP_UPSAMPLE: return op_upsample(f, o);
     case YV7_OP_COPY: return op_copy(f, o);
+    case YV7_OP_ADD: return op_add(f, o);
     default: return fail(YV7_E_ARG, "yv7_forward: unknown op kind");
   }
 }
@@ -347,7 +357,7 @@ int yv7rt::find_chain(const yv7_plan* p, size_t i, const Layout& l, unsigned cha
   if (!forced && !all) return 0;
   auto eligible = [&](size_t j) {
     const auto& o = p->ops[j];
-    return o.kind == YV7_OP_CONV && !is_f8(o) && o.k == 3 && o.s == 1 && o.pad == 1 && !o.pool &&
+    return o.kind == YV7_OP_CONV && !is_f8(o) && o.k == 3 && o.s == 1 && o.pad == 1 && !o.pool && o.src2 < 0 &&
            p->op_variant[j] == (j == i && forced ? 305 : 0) && o.act == p->ops[i].act;
   };
   if (!eligible(i)) return 0;

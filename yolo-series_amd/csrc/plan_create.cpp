@@ -20,6 +20,34 @@ int validate_op(const yv7_net_desc* d, int i, size_t nbytes) {
   const bool src_ok = o.kind == YV7_OP_INPUT || o.kind == YV7_OP_STEM || (o.src >= 0 && o.src < d->n_tensors);
   const bool dst_ok = o.kind == YV7_OP_DETECT || (o.dst >= 0 && o.dst < d->n_tensors);
   if (!src_ok || !dst_ok) return fail(YV7_E_ARG, op + " bad tensor id");
+  if (o.kind < YV7_OP_INPUT || o.kind > YV7_OP_ADD) return fail(YV7_E_ARG, op + " unknown op kind");
+  if (o.kind == YV7_OP_ADD) {
+    if (o.src2 < 0 || o.src2 >= d->n_tensors) return fail(YV7_E_ARG, op + " bad second-operand tensor id");
+    if (o.cout <= 0 || o.cout % vec) return fail(YV7_E_ARG, op + " add channels not a multiple of the vector");
+    if (o.src2_coff < 0 || o.src2_coff % vec || o.src2_coff + o.cout > d->tensors[o.src2].channels)
+      return fail(YV7_E_ARG, op + " second-operand channel slice out of range");
+    if (d->tensors[o.src].shift != d->tensors[o.dst].shift || d->tensors[o.src2].shift != d->tensors[o.dst].shift)
+      return fail(YV7_E_ARG, op + " add operands and result differ in resolution");
+    // (conservative: an exactly in-place add would be safe — a lane reads its vectors before it writes them —
+    // but no graph produces one, and a partial overlap never is)
+    if (overlap(o.dst, o.dst_coff, o.cout, o.src, o.src_coff, o.cout) ||
+        overlap(o.dst, o.dst_coff, o.cout, o.src2, o.src2_coff, o.cout))
+      return fail(YV7_E_ARG, op + " add result overlaps an operand");
+  } else if (o.kind == YV7_OP_CONV && o.src2 != -1) {
+    // the residual of a conv: added at the output's (pixel, channel) in the epilogue of the fp16 tile / ring kernels
+    if (d->dtype != YV7_DT_F16 || o.wfmt != YV7_WFMT_PLAN || o.pool != 0)
+      return fail(YV7_E_ARG, op + " residual needs an fp16 plan, plan-format weights and no pool");
+    if (o.src2 < 0 || o.src2 >= d->n_tensors) return fail(YV7_E_ARG, op + " bad residual tensor id");
+    if (o.cout <= 0 || o.cout % vec) return fail(YV7_E_ARG, op + " residual channels not a multiple of the vector");
+    if (o.src2_coff < 0 || o.src2_coff % vec || o.src2_coff + o.cout > d->tensors[o.src2].channels)
+      return fail(YV7_E_ARG, op + " residual channel slice out of range");
+    if (d->tensors[o.src2].shift != d->tensors[o.dst].shift)
+      return fail(YV7_E_ARG, op + " residual and result differ in resolution");
+    if (overlap(o.dst, o.dst_coff, o.cout, o.src2, o.src2_coff, o.cout))
+      return fail(YV7_E_ARG, op + " residual overlaps the result");
+  } else if (o.src2 != -1) {
+    return fail(YV7_E_ARG, op + " takes no second operand (src2 must be -1)");
+  }
   if (o.kind == YV7_OP_CONV || o.kind == YV7_OP_DETECT) {
     if (o.cin % vec || (o.kind == YV7_OP_CONV && o.cout % vec))
       return fail(YV7_E_ARG, op + " channels not a multiple of the vector");
@@ -73,7 +101,8 @@ bool wants_frag(int dtype, const yv7_op_desc& o) {
   // the Detect head conv with K = 256 / 512 (conv_det_rw_kernel: the weights resident in VGPRs)
   if (dtype == YV7_DT_F16 && o.kind == YV7_OP_DETECT)
     return lr && o.k == 1 && (o.cin == 256 || o.cin == 512) && o.cout <= 256;
-  if (!lr || dtype != YV7_DT_F16 || o.kind != YV7_OP_CONV || is_f8(o) || o.pool || o.cout % 16 || o.cout > 1024)
+  if (!lr || dtype != YV7_DT_F16 || o.kind != YV7_OP_CONV || is_f8(o) || o.pool || o.cout % 16 || o.cout > 1024 ||
+      o.src2 >= 0)   // (a conv with a residual runs the tile / ring kernels only)
     return false;
   if (o.k == 1)   // conv_w1.hip: 1x1 stride 1 with 128 / 256 / 512 inputs
     return o.s == 1 && o.pad == 0 && (o.cin == 128 || o.cin == 256 || o.cin == 512);
@@ -241,6 +270,9 @@ int yv7_set_op_variant(yv7_plan* p, int op, int variant) {
     return fail(YV7_E_ARG, "yv7_set_op_variant: op " + std::to_string(op) + " is not a CONV / DETECT op");
   if (!variant_allowed(o, variant))
     return fail(YV7_E_ARG, "yv7_set_op_variant: variant " + std::to_string(variant) + " is not a kernel configuration");
+  if (o.kind == YV7_OP_CONV && o.src2 >= 0 && variant != 0 && !yv7::conv_f16_variant_has_residual(variant))
+    return fail(YV7_E_ARG, "yv7_set_op_variant: op " + std::to_string(op) + " carries a residual; variant " +
+                               std::to_string(variant) + " is of a kernel family without the residual epilogue");
   p->op_variant[op] = variant;
   return 0;
 }

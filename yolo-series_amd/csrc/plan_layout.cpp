@@ -136,6 +136,13 @@ bool yv7rt::bind_conv(const yv7_plan* p, size_t i, const Layout& l, unsigned cha
   c->y = wsb + l.off[o.dst];
   c->yc = to.channels;
   c->yoff = o.dst_coff;
+  if (o.src2 >= 0) {   // the residual (validate_net: fp16 plan, the output's resolution)
+    const auto& tr = p->tensors[o.src2];
+    c->res = wsb + l.off[o.src2];
+    c->rbytes = (uint32_t)tensor_bytes(p, tr, l.B, l.H, l.W);
+    c->rc = tr.channels;
+    c->roff = o.src2_coff;
+  }
   return c->Ho == (l.H >> to.shift) && c->Wo == (l.W >> to.shift);
 }
 

@@ -192,6 +192,11 @@ struct ConvParams {
   // or null
   const void* wf;
   uint32_t wfbytes;
+  // residual operand of an fp16 conv (null: none): a bordered NHWC tensor of the output's geometry, added at
+  // channels [roff, roff + cout) (pitch rc) after bias and activation; rbytes: its byte size (buffer range)
+  const void* res;
+  uint32_t rbytes;
+  int rc, roff;
 };
 
 // The max-pooled second consumer of a register-streamed 1x1 conv's input (conv_rs.hip): the MP block's
@@ -304,6 +309,10 @@ bool stem_supported(int cin, int ca, int cb, int sa);
 hipError_t launch_stem(const StemParams& p, int x_dtype, hipStream_t st);
 hipError_t launch_copy(int dtype, const void* x, int B, int H, int W, int xc, int xoff, void* y, int yc, int yoff,
                        int C, hipStream_t st);
+// y[.., yoff + c] = a[.., aoff + c] + b[.., boff + c] for c < C over the interiors of three bordered NHWC
+// tensors of one resolution with pitches ac, bc, yc (Shortcut, models/common.py:80-86)
+hipError_t launch_add(int dtype, const void* a, int ac, int aoff, const void* b, int bc, int boff, void* y, int yc,
+                      int yoff, int B, int H, int W, int C, hipStream_t st);
 // nms.hip / preprocess.hip
 size_t nms_workspace_bytes(int B, int N, int no, int multi, int max_nms);
 hipError_t launch_nms(const float* z, const void* rowbest, int B, int N, int no, float conf, float iou, int multi,

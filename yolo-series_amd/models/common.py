@@ -1,8 +1,8 @@
 """Layer modules of the yolov7 family — the reference's layer "plugin" names and parameter trees.
 
-Mirror of the reference interface in models/common.py: class names (Conv, RepConv, SPPCSPC, MP, SP,
-ReOrg, Concat, ImplicitA, ImplicitM) and attribute names (conv, bn, act, rbr_dense, rbr_1x1,
-rbr_identity, rbr_reparam, cv1..cv7, m, implicit) are identical, so reference-keyed state_dicts
+Mirror of the reference interface in models/common.py: class names (Conv, RepConv, SPPCSPC, DownC, MP, SP,
+ReOrg, Concat, Shortcut, ImplicitA, ImplicitM) and attribute names (conv, bn, act, rbr_dense, rbr_1x1,
+rbr_identity, rbr_reparam, cv1..cv7, m, mp, d, implicit) are identical, so reference-keyed state_dicts
  load unchanged.  The modules are parameter containers: the computation of the
 whole network runs on the MI355X through the compiled plan (yv7.graph / libyv7), never layer by
 layer and never on the CPU, so calling a layer directly raises.
@@ -51,6 +51,12 @@ class ReOrg(_PlanOnly):  # common.py:48-53 (x(b,c,w,h) -> y(b,4c,w/2,h/2))
 
 class Concat(_PlanOnly):  # common.py:56-62
     def __init__(self, dimension=1):
+        super().__init__()
+        self.d = dimension
+
+
+class Shortcut(_PlanOnly):  # common.py:80-86 (x[0] + x[1])
+    def __init__(self, dimension=0):
         super().__init__()
         self.d = dimension
 
@@ -145,6 +151,19 @@ class RepConv(_PlanOnly):
             return self.rbr_reparam.weight.detach().float(), self.rbr_reparam.bias.detach().float()
         w, b = self._equivalent()
         return w.detach().float(), b.detach().float()
+
+
+class DownC(_PlanOnly):
+    """Downsampling block of the e6 / d6 / e6e cfgs (common.py:181-192):
+    cat(cv2(cv1(x)), cv3(mp(x))) — a 1x1 + strided 3x3 branch beside a max-pool + 1x1 branch."""
+
+    def __init__(self, c1, c2, n=1, k=2):
+        super().__init__()
+        c_ = int(c1)
+        self.cv1 = Conv(c1, c_, 1, 1)
+        self.cv2 = Conv(c_, c2 // 2, 3, k)
+        self.cv3 = Conv(c1, c2 // 2, 1, 1)
+        self.mp = nn.MaxPool2d(kernel_size=k, stride=k)
 
 
 class SPPCSPC(_PlanOnly):

@@ -25,7 +25,7 @@ from pathlib import Path
 import torch
 import torch.nn as nn
 
-from models.common import (MP, SP, Concat, Conv, ImplicitA, ImplicitM, ReOrg, RepConv, SPPCSPC)
+from models.common import (MP, SP, Concat, Conv, DownC, ImplicitA, ImplicitM, ReOrg, RepConv, Shortcut, SPPCSPC)
 from utils.general import make_divisible
 from utils.torch_utils import initialize_weights, model_info, scale_img
 
@@ -119,7 +119,8 @@ class IAuxDetect(IDetect):
 
 # The layer "plugin registry": names the cfg may use (the reference resolves them with eval(), yolo.py:744).
 MODULES = {
-    'Conv': Conv, 'RepConv': RepConv, 'SPPCSPC': SPPCSPC, 'MP': MP, 'SP': SP, 'ReOrg': ReOrg, 'Concat': Concat,
+    'Conv': Conv, 'RepConv': RepConv, 'SPPCSPC': SPPCSPC, 'DownC': DownC, 'MP': MP, 'SP': SP, 'ReOrg': ReOrg,
+    'Concat': Concat, 'Shortcut': Shortcut,
     'Detect': Detect, 'IDetect': IDetect, 'IAuxDetect': IAuxDetect, 'nn.Upsample': nn.Upsample,
     'nn.Conv2d': nn.Conv2d, 'nn.BatchNorm2d': nn.BatchNorm2d,
 }
@@ -158,18 +159,20 @@ def parse_model(d, ch):
         mod = MODULES[m]
         args = [_resolve_arg(a, nc, anchors) for a in args]
         n = max(round(n * gd), 1) if n > 1 else n
-        if mod in (nn.Conv2d, Conv, RepConv, SPPCSPC):
+        if mod in (nn.Conv2d, Conv, RepConv, DownC, SPPCSPC):
             c1, c2 = ch[f], args[0]
             if c2 != no:
                 c2 = make_divisible(c2 * gw, 8)
             args = [c1, c2, *args[1:]]
-            if mod is SPPCSPC:
+            if mod in (DownC, SPPCSPC):
                 args.insert(2, n)
                 n = 1
         elif mod is nn.BatchNorm2d:
             args = [ch[f]]
         elif mod is Concat:
             c2 = sum(ch[x] for x in f)
+        elif mod is Shortcut:
+            c2 = ch[f[0]]
         elif mod in (Detect, IDetect, IAuxDetect):
             args.append([ch[x] for x in f])
             if isinstance(args[1], int):
@@ -199,7 +202,7 @@ def _levels(layers):
         elif isinstance(m, RepConv) and (m.rbr_reparam.stride[0] if hasattr(m, 'rbr_reparam')
                                          else m.rbr_dense[0].stride[0]) == 2:
             prev += 1
-        elif isinstance(m, (MP, ReOrg)):
+        elif isinstance(m, (MP, ReOrg, DownC)):
             prev += 1
         elif isinstance(m, nn.Upsample):
             prev -= 1

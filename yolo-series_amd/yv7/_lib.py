@@ -13,11 +13,11 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libyv7.so')
 
-ABI_VERSION = 4
+ABI_VERSION = 5
 BORDER = 1          # zero frame around every workspace tensor (YV7_BORDER)
 DT_F32, DT_F16 = 0, 1
 ACT_NONE, ACT_SILU, ACT_LEAKY = 0, 1, 2
-OP_INPUT, OP_CONV, OP_MAXPOOL, OP_UPSAMPLE, OP_COPY, OP_DETECT, OP_STEM = 0, 1, 2, 3, 4, 5, 6
+OP_INPUT, OP_CONV, OP_MAXPOOL, OP_UPSAMPLE, OP_COPY, OP_DETECT, OP_STEM, OP_ADD = 0, 1, 2, 3, 4, 5, 6, 7
 WFMT_PLAN, WFMT_FP8 = 0, 1
 
 
@@ -35,7 +35,14 @@ class OpDesc(ctypes.Structure):
                 ('cout2', ctypes.c_int32), ('act2', ctypes.c_int32),
                 ('w2_off', ctypes.c_int64), ('b2_off', ctypes.c_int64),
                 ('wfmt', ctypes.c_int32), ('xscale', ctypes.c_float), ('s_off', ctypes.c_int64),
-                ('pool', ctypes.c_int32), ('reserved', ctypes.c_int32)]
+                ('pool', ctypes.c_int32), ('reserved', ctypes.c_int32),
+                ('src2', ctypes.c_int32), ('src2_coff', ctypes.c_int32)]
+
+    def __init__(self, *args, **kw):
+        # no second operand unless the caller names one, by keyword or position (0 would be tensor 0)
+        if len(args) <= [f[0] for f in self._fields_].index('src2'):
+            kw.setdefault('src2', -1)
+        super().__init__(*args, **kw)
 
 
 class NetDesc(ctypes.Structure):

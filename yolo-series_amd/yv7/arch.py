@@ -1,8 +1,8 @@
 """Model graph definitions for the yolov7 family, built as dicts in the reference's cfg schema.
 
 The reference describes each network as a YAML file (`cfg/deploy/yolov7.yaml`,
-`cfg/deploy/yolov7-tiny.yaml`, `cfg/deploy/yolov7-w6.yaml`, and the `cfg/training/*` twins that
-differ only in the head).  The GPU box has no copy of the reference, so the graphs are generated
+`cfg/deploy/yolov7-tiny.yaml`, `cfg/deploy/yolov7-w6.yaml`, `-e6.yaml`, `-d6.yaml`, `-e6e.yaml`, and the
+`cfg/training/*` twins that differ only in the head).  The GPU box has no copy of the reference, so the graphs are generated
 here from their building blocks (stem, E-ELAN, MP-downsample, SPPCSPC, route/upsample, heads).
 The result is the same dict `yaml.safe_load` returns for those files (module names and string
 arguments such as 'None', 'nc', 'anchors', 'nn.LeakyReLU(0.1)' included), so `parse_model`
@@ -116,6 +116,93 @@ def yolov7_w6(head='Detect'):
     return d
 
 
+W6_ANCHORS = [[19, 27, 44, 40, 38, 94], [96, 68, 86, 152, 180, 137], [140, 301, 303, 264, 238, 542],
+              [436, 615, 739, 380, 925, 792]]
+
+
+def _elan_deep(c, out, n3, first=(-1, -2)):
+    """E-ELAN block of the e6 / d6 / e6e backbones: 2 x 1x1 split (read from `first`), n3 x 3x3 chain, every
+    second 3x3 and both splits into the concat, 1x1 (cfg/deploy/yolov7-e6.yaml:20-29, yolov7-d6.yaml:20-31)."""
+    cat = [-1 - 2 * j for j in range(n3 // 2 + 1)] + [-(n3 + 2)]
+    return [_conv(first[0], c), _conv(first[1], c)] + [_conv(-1, c, 3) for _ in range(n3)] + \
+        [[cat, 1, 'Concat', [1]], _conv(-1, out)]
+
+
+def _elan_deep_head(c1, c2, out, n3, first=(-1, -2)):
+    """E-ELAN-H block of the e6 / d6 / e6e necks: every layer of the block into the concat
+    (cfg/deploy/yolov7-e6.yaml:89-98)."""
+    cat = [-j for j in range(1, n3 + 3)]
+    return [_conv(first[0], c1), _conv(first[1], c1)] + [_conv(-1, c2, 3) for _ in range(n3)] + \
+        [[cat, 1, 'Concat', [1]], _conv(-1, out)]
+
+
+def _twice(block, n3):
+    """e6e's doubled block: the same block again from the same input, the two outputs joined by a
+    residual Shortcut (cfg/deploy/yolov7-e6e.yaml:20-40)."""
+    n = n3 + 5   # layers of one block + 1: the second block's splits reach back over the first
+    return block((-1, -2)) + block((-n, -n - 1)) + [[[-1, -n], 1, 'Shortcut', [1]]]
+
+
+def _p6_deep(head, stem, widths, n3, neck, double):
+    """The e6 / d6 / e6e graph: ReOrg + 3x3 stem, five DownC + E-ELAN stages, SPPCSPC, a three-step top-down
+    and a three-step bottom-up (DownC) neck, four 3x3 output convs (+ four auxiliary ones for IAuxDetect).
+    widths: per backbone stage (ELAN hidden width, stage width); neck: per level P6, P5, P4, P3 (block
+    width, split width, 3x3 width); double: every block twice with a Shortcut (e6e)."""
+    layers = []
+
+    def add(block):
+        layers.extend(_twice(block, n3) if double else block((-1, -2)))
+        return len(layers) - 1
+
+    layers += [[-1, 1, 'ReOrg', []], _conv(-1, stem, 3)]
+    bb_out = []
+    for c, out in widths:
+        layers.append([-1, 1, 'DownC', [out]])
+        bb_out.append(add(lambda first, c=c, out=out: _elan_deep(c, out, n3, first)))
+    n_bb = len(layers)
+    layers.append([-1, 1, 'SPPCSPC', [neck[0][0]]])
+    td_out, aux_src = [len(layers) - 1], [len(layers) - 1]
+    for lvl in (1, 2, 3):
+        r, c1, c2 = neck[lvl]
+        layers += [_conv(-1, r), UP, _conv(bb_out[4 - lvl], r), [[-1, -2], 1, 'Concat', [1]]]
+        td_out.append(add(lambda first, r=r, c1=c1, c2=c2: _elan_deep_head(c1, c2, r, n3, first)))
+        aux_src.append(td_out[-1] - 1 if double else td_out[-1])   # e6e: the block's own output, before the Shortcut
+    outs = [td_out[-1]]
+    for lvl in (2, 1, 0):
+        r, c1, c2 = neck[lvl]
+        layers += [[-1, 1, 'DownC', [r]], [[-1, td_out[lvl]], 1, 'Concat', [1]]]
+        outs.append(add(lambda first, r=r, c1=c1, c2=c2: _elan_deep_head(c1, c2, r, n3, first)))
+    first_out = len(layers)
+    layers += [_conv(o, 2 * layers[o - 1 if double else o][3][0], 3) for o in outs]
+    det = list(range(first_out, first_out + 4))
+    if head == 'IAuxDetect':
+        layers += [_conv(a, 2 * layers[a][3][0], 3) for a in reversed(aux_src)]
+        det += list(range(first_out + 4, first_out + 8))
+    layers.append([det, 1, head, ['nc', 'anchors']])
+    d = _params(copy.deepcopy(W6_ANCHORS))
+    d['backbone'], d['head'] = layers[:n_bb], layers[n_bb:]
+    return d
+
+
+def yolov7_e6(head='Detect'):
+    """yolov7-e6 P6 (cfg/deploy/yolov7-e6.yaml; head='IAuxDetect' gives cfg/training/yolov7-e6.yaml)."""
+    return _p6_deep(head, 80, [(64, 160), (128, 320), (256, 640), (384, 960), (512, 1280)], 6,
+                    [(640, 512, 256), (480, 384, 192), (320, 256, 128), (160, 128, 64)], False)
+
+
+def yolov7_d6(head='Detect'):
+    """yolov7-d6 P6 (cfg/deploy/yolov7-d6.yaml; head='IAuxDetect' gives cfg/training/yolov7-d6.yaml)."""
+    return _p6_deep(head, 96, [(64, 192), (128, 384), (256, 768), (384, 1152), (512, 1536)], 8,
+                    [(768, 512, 256), (576, 384, 192), (384, 256, 128), (192, 128, 64)], False)
+
+
+def yolov7_e6e(head='Detect'):
+    """yolov7-e6e P6 (cfg/deploy/yolov7-e6e.yaml; head='IAuxDetect' gives cfg/training/yolov7-e6e.yaml): e6 with
+    every E-ELAN block doubled and joined by a residual Shortcut (models/common.py:80-86)."""
+    return _p6_deep(head, 80, [(64, 160), (128, 320), (256, 640), (384, 960), (512, 1280)], 6,
+                    [(640, 512, 256), (480, 384, 192), (320, 256, 128), (160, 128, 64)], True)
+
+
 # name -> (builder, head) ; "-train" variants mirror cfg/training/*.yaml
 REGISTRY = {
     'yolov7': (yolov7, 'Detect'),
@@ -124,6 +211,12 @@ REGISTRY = {
     'yolov7-train': (yolov7, 'IDetect'),
     'yolov7-tiny-train': (yolov7_tiny, 'IDetect'),
     'yolov7-w6-train': (yolov7_w6, 'IAuxDetect'),
+    'yolov7-e6': (yolov7_e6, 'Detect'),
+    'yolov7-d6': (yolov7_d6, 'Detect'),
+    'yolov7-e6e': (yolov7_e6e, 'Detect'),
+    'yolov7-e6-train': (yolov7_e6, 'IAuxDetect'),
+    'yolov7-d6-train': (yolov7_d6, 'IAuxDetect'),
+    'yolov7-e6e-train': (yolov7_e6e, 'IAuxDetect'),
 }
 
 

@@ -7,6 +7,11 @@ kernel launch:
                               the -inf padding clips identically), concats as channel slices (common.py:276-280)
   MP / SP                  -> MAXPOOL(k, k, 0) / MAXPOOL(k, s, k//2)
   nn.Upsample(x2 nearest)  -> UPSAMPLE
+  DownC                    -> 3 CONV + MAXPOOL(2): cv1 into a private tensor, cv2 (3x3 stride 2) and mp + cv3 into the two
+                              halves of the layer's output slice (common.py:181-192); fp16 plans fold mp + cv3 into
+                              one pooled conv where _fold_pools' conditions hold
+  Shortcut                 -> ADD (dst = src + src2, common.py:80-86); fp16 plans: folded into the conv that produces
+                              one operand, as that conv's residual, where _fold_shortcuts' rule says it pays
   Concat                   -> nothing: producers write their channel slice of the concat tensor directly;
                               an input that already lives in another concat (or is the input image) gets a COPY
   ReOrg at layer 0         -> fused into the INPUT packing op (space-to-depth while converting NCHW -> NHWC);
@@ -25,7 +30,7 @@ from dataclasses import dataclass, field
 import torch
 import torch.nn as nn
 
-from models.common import MP, SP, SPPCSPC, Concat, Conv, ReOrg, RepConv
+from models.common import MP, SP, SPPCSPC, Concat, Conv, DownC, ReOrg, RepConv, Shortcut
 from models.yolo import Detect
 from yv7 import _lib as L
 
@@ -129,7 +134,7 @@ def fp8_weight_scales(wk: torch.Tensor) -> torch.Tensor:
 def fp8_eligible(g: Graph, o: dict) -> bool:
     """CONV ops an fp8 plan runs in e4m3: 1x1 stride-1 convs of an fp16 plan (the Detect head stays fp16)."""
     return (g.dtype == L.DT_F16 and o['kind'] == L.OP_CONV and o['k'] == 1 and o['s'] == 1 and o['pad'] == 0
-            and o['cout'] <= 1024)
+            and o['cout'] <= 1024 and 'src2' not in o)   # (a conv that carries a residual stays fp16)
 
 
 # fp8 pays only on wide layers: measured per op on MI355X (bs32 640 yolov7, scripts/op_profile.py
@@ -237,6 +242,12 @@ def compile_model(model, dtype: int, fp8=None) -> Graph:
             ch[i], shift[i] = c.out_channels, ps[0] + (1 if c.stride[0] == 2 else 0)
         elif isinstance(m, SPPCSPC):
             ch[i], shift[i] = m.cv7.conv.out_channels, ps[0]
+        elif isinstance(m, DownC):
+            ch[i], shift[i] = m.cv2.conv.out_channels + m.cv3.conv.out_channels, ps[0] + 1
+        elif isinstance(m, Shortcut):
+            if len(prev) != 2 or pc[0] != pc[1] or ps[0] != ps[1]:
+                raise ValueError(f'layer {i}: Shortcut needs two inputs of equal channels and resolution')
+            ch[i], shift[i] = pc[0], ps[0]
         elif isinstance(m, MP):
             ch[i], shift[i] = pc[0], ps[0] + 1
         elif isinstance(m, SP):
@@ -275,7 +286,7 @@ def compile_model(model, dtype: int, fp8=None) -> Graph:
         loc[0] = (t_in, 0)
 
     # ---- pass 2: concat placement (producers write straight into the concat tensor)
-    placeable = (Conv, RepConv, SPPCSPC, MP, SP, nn.Upsample)
+    placeable = (Conv, RepConv, SPPCSPC, DownC, Shortcut, MP, SP, nn.Upsample)
     placed = set()
     for m in layers:
         if isinstance(m, Concat) and live[m.i]:
@@ -372,6 +383,33 @@ def compile_model(model, dtype: int, fp8=None) -> Graph:
             cv(6, (t5, 0, c_), (cat2, 0))
             cv(2, src, (cat2, c_))
             cv(7, (cat2, 0, 2 * c_), out_of(i))
+        elif isinstance(m, DownC):
+            src = src_of(i, m.f)
+            cs, c_, ch2 = src[2], m.cv1.conv.out_channels, m.cv2.conv.out_channels
+            k = m.mp.kernel_size if isinstance(m.mp.kernel_size, int) else m.mp.kernel_size[0]
+            if k != 2 or cs % V or c_ % V or ch2 % V:
+                raise NotImplementedError('DownC: k = 2 and widths that are multiples of the vector width only')
+            td, do = out_of(i)
+            t1 = g.add_tensor(c_, shift[i] - 1)
+            tp = g.add_tensor(cs, shift[i])
+
+            def cv(j, a, d):
+                mod = getattr(m, f'cv{j}')
+                w, b = mod.fused_weight_bias()
+                c = mod.conv
+                conv_op(a, d, w, b, c.kernel_size[0], c.stride[0], c.padding[0], _act_code(mod.act), (i, j))
+
+            cv(1, src, (t1, 0))
+            cv(2, (t1, 0, c_), (td, do))
+            g.ops.append(dict(kind=L.OP_MAXPOOL, src=src[0], src_coff=src[1], dst=tp, dst_coff=0, cout=cs, k=2, s=2,
+                              pad=0))
+            cv(3, (tp, 0, cs), (td, do + ch2))
+        elif isinstance(m, Shortcut):
+            (ta, oa, ca), (tb, ob, _), (td, do) = src_of(i, m.f[0]), src_of(i, m.f[1]), out_of(i)
+            if ca % V:
+                raise NotImplementedError('Shortcut width not a multiple of the vector width')
+            g.ops.append(dict(kind=L.OP_ADD, src=ta, src_coff=oa, src2=tb, src2_coff=ob, dst=td, dst_coff=do, cout=ca,
+                              layer=i))
         elif isinstance(m, (MP, SP)):
             (ts, so, cs), (td, do) = src_of(i, m.f), out_of(i)
             p = m.m
@@ -403,6 +441,8 @@ def compile_model(model, dtype: int, fp8=None) -> Graph:
                 g.ops.append(dict(kind=L.OP_DETECT, src=ts, src_coff=so, cin=_rup(cs, V), dst=-1, cout=w.shape[0],
                                   k=1, s=1, pad=0, level=lvl, w_off=w_off, b_off=b_off))
     folded = _fold_pools(g) if dtype == L.DT_F16 and os.environ.get('YV7_NO_POOLFOLD') != '1' else []
+    if dtype == L.DT_F16 and os.environ.get('YV7_NO_RESFUSE') != '1':
+        folded += _fold_shortcuts(g, loc)
     if os.environ.get('YV7_NO_MERGE') != '1':
         _merge_siblings(g)
         if os.environ.get('YV7_NO_TMERGE') != '1':
@@ -435,12 +475,12 @@ def _fold_pools(g: Graph):
             i += 1
             continue
         t = mp['dst']
-        readers = [j for j, o in enumerate(g.ops) if j != i and o.get('src', -1) == t]
+        readers = [j for j, o in enumerate(g.ops) if j != i and t in (o.get('src', -1), o.get('src2', -1))]
         writers = [j for j, o in enumerate(g.ops) if j != i and _writes(o) and _writes(o)[0] == t]
         ok = len(readers) == 1 and not writers and readers[0] > i
         if ok:
             c = g.ops[readers[0]]
-            ok = (c['kind'] == L.OP_CONV and '_w' in c and c['k'] == 1 and c['s'] == 1 and c['pad'] == 0 and
+            ok = (c['kind'] == L.OP_CONV and '_w' in c and c['src'] == t and c['k'] == 1 and c['s'] == 1 and c['pad'] == 0 and
                   c['src_coff'] == mp['dst_coff'] and c['cin'] == mp['cout'] and c['cin'] % 64 == 0 and
                   c['cin'] <= 512)   # deep-K (1024) pairs run faster unfused (csrc/conv_f16.hip, pool dispatch)
         if not ok:
@@ -450,6 +490,84 @@ def _fold_pools(g: Graph):
         folded.append(mp.get('layer'))
         del g.ops[i]
     return folded
+
+
+def _reads(o):
+    """The (tensor, first channel, channels) slices an op reads."""
+    r = []
+    if o.get('src', -1) >= 0:
+        r.append((o['src'], o.get('src_coff', 0), o['cin'] if o['kind'] in (L.OP_CONV, L.OP_DETECT) else o['cout']))
+    if o.get('src2', -1) >= 0:
+        r.append((o['src2'], o['src2_coff'], o['cout']))
+    return r
+
+
+# Shapes (output channels, log2 stride) whose Shortcut runs folded into its producer by default: those where the
+# fused launch measured faster than conv + add by more than the run-to-run spread (DESIGN.md §4.17, yolov7-e6e
+# 1280 x 1280 bs 8).  YV7_RESFUSE=1 folds every eligible Shortcut, YV7_NO_RESFUSE=1 none.
+RESFUSE_SHAPES = frozenset({(160, 2), (160, 3), (480, 5), (640, 6), (1280, 6)})
+
+
+def _fold_shortcuts(g: Graph, loc: dict):
+    """ADD (Shortcut, models/common.py:80-86) whose one operand is the whole output of a plain CONV (not pooled,
+    not a STEM; it runs before the sibling merges and such a conv never merges; fp8 never takes it) that nothing
+    else reads -> that conv takes the other operand as its residual (src2) and writes the ADD's destination: the
+    conv's epilogue adds it in fp32 and rounds once (csrc/conv_f16_ring.hip), the ADD and the conv's own output
+    tensor disappear.  The residual must be complete before the conv runs and must not overlap the destination;
+    nothing between the conv and the ADD may touch the destination.  Returns the layers whose outputs no longer
+    exist as tensors."""
+    every = os.environ.get('YV7_RESFUSE') == '1'
+    folded = []
+    a = 0
+    while a < len(g.ops):
+        add = g.ops[a]
+        done = False
+        if add['kind'] == L.OP_ADD and (every or (add['cout'], g.tensors[add['dst']][1]) in RESFUSE_SHAPES):
+            dst = (add['dst'], add['dst_coff'], add['cout'])
+            for mine, other in ((('src', 'src_coff'), ('src2', 'src2_coff')), (('src2', 'src2_coff'), ('src', 'src_coff'))):
+                own = (add[mine[0]], add[mine[1]], add['cout'])
+                res = (add[other[0]], add[other[1]], add['cout'])
+                writers = [j for j, o in enumerate(g.ops) if _writes(o) and _overlaps(*_writes(o), *own)]
+                readers = [j for j, o in enumerate(g.ops) if any(_overlaps(*r, *own) for r in _reads(o))]
+                if len(writers) != 1 or readers != [a] or writers[0] > a:
+                    continue
+                c = g.ops[writers[0]]
+                if not (c['kind'] == L.OP_CONV and '_w' in c and not c.get('pool') and 'src2' not in c and
+                        _writes(c) == own and c['dst_coff'] == 0 and g.tensors[c['dst']][0] == c['cout']):
+                    continue
+                if _overlaps(*res, *dst) or _overlaps(*own, *res):
+                    continue
+                # the residual is complete before the conv; between the conv and the ADD nothing touches the
+                # destination
+                if any(_writes(o) and _overlaps(*_writes(o), *res) for o in g.ops[writers[0]:a]):
+                    continue
+                if any((_writes(o) and _overlaps(*_writes(o), *dst)) or any(_overlaps(*r, *dst) for r in _reads(o))
+                       for o in g.ops[writers[0] + 1:a]):
+                    continue
+                dead = c['dst']
+                c.update(dst=add['dst'], dst_coff=add['dst_coff'], src2=res[0], src2_coff=res[1])
+                del g.ops[a]
+                for lay, _ in c['layers']:
+                    folded.append(lay)
+                    loc.pop(lay, None)
+                _drop_tensor(g, loc, dead)
+                done = True
+                break
+        if not done:
+            a += 1
+    return folded
+
+
+def _drop_tensor(g: Graph, loc: dict, t: int):
+    """Remove tensor t, which no op touches any more (higher ids shift down in every op and in loc)."""
+    for o in g.ops:
+        for k in ('src', 'src2', 'dst'):
+            assert o.get(k, -1) != t
+            if o.get(k, -1) > t:
+                o[k] -= 1
+    for k, (tt, off) in list(loc.items()):
+        loc[k] = (tt - 1 if tt > t else tt, off)
+    del g.tensors[t]
 
 
 def _overlaps(t, lo, n, t2, lo2, n2):
@@ -470,14 +588,14 @@ def _merge_sibling_tensors(g: Graph, loc: dict):
     i = 0
     while i < len(g.ops):
         a = g.ops[i]
-        if a['kind'] != L.OP_CONV or '_w' not in a:
+        if a['kind'] != L.OP_CONV or '_w' not in a or 'src2' in a:
             i += 1
             continue
         merged = False
         for j in range(i + 1, len(g.ops)):
             b = g.ops[j]
             wb = _writes(b)
-            if (b['kind'] == L.OP_CONV and '_w' in b and all(a.get(k) == b.get(k) for k in key) and
+            if (b['kind'] == L.OP_CONV and '_w' in b and 'src2' not in b and all(a.get(k) == b.get(k) for k in key) and
                     b['dst'] != a['dst'] and g.tensors[a['dst']][1] == g.tensors[b['dst']][1]):
                 ca, cb = g.tensors[a['dst']][0], g.tensors[b['dst']][0]
                 if a['dst_coff'] + a['cout'] == ca and b['dst_coff'] == 0:
@@ -498,6 +616,9 @@ def _merge_sibling_tensors(g: Graph, loc: dict):
                         if o.get('src', -1) >= 0 and _overlaps(o['src'], o.get('src_coff', 0),
                                                                max(o.get('cin', 0), o.get('cout', 0)),
                                                                b['dst'], b['dst_coff'], b['cout']):
+                            ok = False
+                        if o.get('src2', -1) >= 0 and _overlaps(o['src2'], o['src2_coff'], o['cout'],
+                                                                b['dst'], b['dst_coff'], b['cout']):
                             ok = False
                     if ok:
                         _fuse_tensors(g, loc, first['dst'], second['dst'])
@@ -533,6 +654,8 @@ def _fuse_tensors(g: Graph, loc: dict, t1: int, t2: int):
     for o in g.ops:
         if o.get('src', -1) >= 0:
             o['src'], o['src_coff'] = remap(o['src'], o.get('src_coff', 0))
+        if o.get('src2', -1) >= 0:
+            o['src2'], o['src2_coff'] = remap(o['src2'], o.get('src2_coff', 0))
         if o.get('dst', -1) >= 0:
             o['dst'], o['dst_coff'] = remap(o['dst'], o.get('dst_coff', 0))
     for k, (t, off) in list(loc.items()):
@@ -546,7 +669,7 @@ def _writes(o):
         return None
     if o['kind'] == L.OP_STEM:
         return o['dst'], o['dst_coff'], o['cout2']
-    return o['dst'], o['dst_coff'], o['cout']
+    return o['dst'], o.get('dst_coff', 0), o['cout']   # (INPUT names no offset: it writes tensor 0 whole)
 
 
 def _merge_siblings(g: Graph):
@@ -561,13 +684,13 @@ def _merge_siblings(g: Graph):
     i = 0
     while i < len(g.ops):
         a = g.ops[i]
-        if a['kind'] != L.OP_CONV or '_w' not in a:
+        if a['kind'] != L.OP_CONV or '_w' not in a or 'src2' in a:
             i += 1
             continue
         for j in range(i + 1, len(g.ops)):
             b = g.ops[j]
             w = _writes(b)
-            if b['kind'] == L.OP_CONV and '_w' in b and all(a[k] == b[k] for k in key):
+            if b['kind'] == L.OP_CONV and '_w' in b and 'src2' not in b and all(a[k] == b[k] for k in key):
                 if b['dst_coff'] == a['dst_coff'] + a['cout']:
                     lo, hi = a, b
                 elif a['dst_coff'] == b['dst_coff'] + b['cout']:
@@ -587,6 +710,9 @@ def _merge_siblings(g: Graph):
                         rs = o.get('src', -1)
                         if rs == b['dst'] and o.get('src_coff', 0) < b['dst_coff'] + b['cout'] and \
                                 b['dst_coff'] < o.get('src_coff', 0) + max(o.get('cin', 0), o.get('cout', 0)):
+                            ok = False
+                        if o.get('src2', -1) >= 0 and _overlaps(o['src2'], o['src2_coff'], o['cout'],
+                                                                b['dst'], b['dst_coff'], b['cout']):
                             ok = False
                     if ok:
                         m = dict(a)

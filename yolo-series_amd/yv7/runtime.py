@@ -81,6 +81,19 @@ def kernel_key(name: str) -> str:
     return n
 
 
+def op_descs(graph):
+    """The yv7_op_desc records of a compiled graph; a field an op does not name takes its neutral value
+    (src2 = -1: no second operand)."""
+    ops = []
+    for o in graph.ops:
+        d = dict(kind=0, src=0, src_coff=0, cin=0, dst=0, dst_coff=0, cout=0, k=1, s=1, pad=0, act=0, level=0,
+                 w_off=0, b_off=0, cout2=0, act2=0, w2_off=0, b2_off=0, wfmt=0, xscale=0.0, s_off=0, pool=0,
+                 src2=-1, src2_coff=0)
+        d.update({k: v for k, v in o.items() if k in d})
+        ops.append(L.OpDesc(**d))
+    return ops
+
+
 class Plan:
     def __init__(self, graph, device, weights: torch.Tensor):
         self.graph = graph
@@ -89,12 +102,7 @@ class Plan:
         self.nl, self.na, self.no = graph.nl, graph.na, graph.no
         lib = L.lib()
         self._tensors = (L.TensorDesc * len(graph.tensors))(*[L.TensorDesc(c, s) for c, s in graph.tensors])
-        ops = []
-        for o in graph.ops:
-            d = dict(kind=0, src=0, src_coff=0, cin=0, dst=0, dst_coff=0, cout=0, k=1, s=1, pad=0, act=0, level=0,
-                     w_off=0, b_off=0, cout2=0, act2=0, w2_off=0, b2_off=0, wfmt=0, xscale=0.0, s_off=0, pool=0)
-            d.update({k: v for k, v in o.items() if k in d})
-            ops.append(L.OpDesc(**d))
+        ops = op_descs(graph)
         self._ops = (L.OpDesc * len(ops))(*ops)
         self._stride = (ctypes.c_float * graph.nl)(*graph.stride)
         self._anchors = (ctypes.c_float * len(graph.anchor_grid))(*graph.anchor_grid)
@@ -292,13 +300,17 @@ class Plan:
                 # an MP folded into the conv (pool 2): the reference-boundary bytes of both layers, i.e.
                 # also the pooled tensor's write and re-read
                 mp = 2 * B * Ho * Wo * cin * es if o.get('pool', 0) == 2 else 0
-                out.append((kind, flops, B * Hi * Wi * cin * es + obytes + wbytes + mp))
+                res = B * Ho * Wo * cout * es if o.get('src2', -1) >= 0 else 0   # a residual: one extra read
+                out.append((kind, flops, B * Hi * Wi * cin * es + obytes + wbytes + mp + res))
             elif kind == L.OP_MAXPOOL:
                 c = o['cout']
                 out.append((kind, 0.0, B * Hi * Wi * c * es + B * Ho * Wo * c * es))
             elif kind == L.OP_UPSAMPLE:
                 c = o['cout']
                 out.append((kind, 0.0, B * Hi * Wi * c * es + B * 4 * Hi * Wi * c * es))
+            elif kind == L.OP_ADD:   # two operands read, the sum written
+                c = o['cout']
+                out.append((kind, 0.0, 3 * B * Hi * Wi * c * es))
             else:
                 c = o['cout']
                 out.append((kind, 0.0, 2 * B * Hi * Wi * c * es))

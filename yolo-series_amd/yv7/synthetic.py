@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from models.common import MP, SP, SPPCSPC, Concat, Conv, ReOrg, RepConv
+from models.common import MP, SP, SPPCSPC, Concat, Conv, DownC, ReOrg, RepConv, Shortcut
 from models.yolo import Detect, IDetect
 
 class _Gen:
@@ -128,6 +128,12 @@ def synthetic_state_dict(model, seed=0, head_gain=2.0, target_candidates=0.06, c
             y1 = _calib_conv(gen, m.cv6, _calib_conv(gen, m.cv5, cat, **bnkw), **bnkw)
             y2 = _calib_conv(gen, m.cv2, x, **bnkw)
             x = _calib_conv(gen, m.cv7, torch.cat((y1, y2), 1), **bnkw)
+        elif isinstance(m, DownC):
+            a = _calib_conv(gen, m.cv2, _calib_conv(gen, m.cv1, x, **bnkw), **bnkw)
+            b = _calib_conv(gen, m.cv3, F.max_pool2d(x, m.mp.kernel_size, m.mp.stride), **bnkw)
+            x = torch.cat((a, b), 1)
+        elif isinstance(m, Shortcut):
+            x = x[0] + x[1]
         elif isinstance(m, MP):
             x = F.max_pool2d(x, m.m.kernel_size, m.m.stride)
         elif isinstance(m, SP):
