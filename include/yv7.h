@@ -21,6 +21,10 @@
  *                     utils/add_nms.py:94-138 (fixed-shape num_dets/boxes/scores/classes)
  *   yv7_letterbox     letterbox() + the detect.py input         utils/datasets.py:1277-1307,
  *                     conversion                                detect.py:100-104, datasets.py:199
+ *   yv7_letterbox_ragged  the same for frames of different    models/common.py:899-918 (autoShape's
+ *                     sizes on one canvas                       letterbox loop, np.stack, transpose, / 255)
+ *   yv7_scale_boxes   scale_coords() + clip_coords(),           utils/general.py:340-361, detect.py:183,
+ *                     .round(), the Detections views            models/common.py:940-948
  */
 #ifndef YV7_H
 #define YV7_H
@@ -217,6 +221,42 @@ size_t yv7_letterbox_workspace_bytes(int new_h, int new_w);
 int yv7_letterbox(const void* src, int B, int H, int W, int new_h, int new_w, int top, int left, int out_h,
                   int out_w, int pad_b, int pad_g, int pad_r, int out_kind, void* dst, void* workspace,
                   size_t ws_bytes, void* stream);
+
+/* Ragged letterbox (replaces models/common.py:899-918, autoShape's per-image letterbox() loop with np.stack,
+ * transpose((0, 3, 1, 2)) and / 255; and a detect.py loop that batches files of different sizes): B frames,
+ * each with its own size and host-computed geometry, onto one out_h x out_w canvas in one call.  Per frame the
+ * arithmetic is yv7_letterbox's (identity, bilinear or exact-2x area, chosen per frame), bit for bit.
+ * frames is a host array the caller may free on return: the descriptors travel to the kernel by value,
+ * 64 per launch, and the call is asynchronous on `stream` without any device synchronisation.
+ * (pad0, pad1, pad2) is the canvas colour in the input's channel order.  out_kind as yv7_letterbox; the float
+ * kinds write planes in the input's channel order (swap_rb = 0: RGB frames, autoShape) or reversed (swap_rb = 1:
+ * BGR frames -> RGB planes, detect.py).  The coefficients are computed inline, so the workspace size is 0
+ * and workspace may be null. */
+typedef struct {
+  const void* data;                /* device pointer, uint8 [h][w][3], packed rows */
+  int32_t h, w;                    /* source size */
+  int32_t new_h, new_w, top, left; /* resized size and its place on the canvas */
+} yv7_frame_desc;
+
+size_t yv7_letterbox_ragged_workspace_bytes(const yv7_frame_desc* frames, int B);
+int yv7_letterbox_ragged(const yv7_frame_desc* frames, int B, int out_h, int out_w, int pad0, int pad1, int pad2,
+                         int swap_rb, int out_kind, void* dst, void* workspace, size_t ws_bytes, void* stream);
+
+/* Boxes back to image pixels (replaces utils/general.py:340-361 scale_coords(ratio_pad=None) + clip_coords,
+ * detect.py:183's .round() and the derived views of Detections.__init__, models/common.py:940-948) on yv7_nms's
+ * fixed-shape output, without a host sync.  Per row < count[b] of det [B,max_det,6], in place: columns 0, 2
+ * = (x - pad_w) / gain clamped to [0, w0], columns 1, 3 = (y - pad_h) / gain clamped to [0, h0] (IEEE fp32
+ * division), then rounded half to even if round_boxes.  The host computes gain = min(h1 / h0, w1 / w0),
+ * pad_w = (w1 - w0 * gain) / 2 and pad_h = (h1 - h0 * gain) / 2 in double and narrows them once.
+ * xywh (centre, size), xyxyn and xywhn (the two divided by (w0, h0, w0, h0, 1, 1)): nullable [B,max_det,6];
+ * their rows >= count[b] are zeroed, det's are left alone.  images is a host array, passed on by value. */
+typedef struct {
+  int32_t h0, w0; /* the image's own size */
+  float gain, pad_w, pad_h;
+} yv7_scale_desc;
+
+int yv7_scale_boxes(float* det, const int32_t* count, int B, int max_det, const yv7_scale_desc* images,
+                    int round_boxes, float* xywh, float* xyxyn, float* xywhn, void* stream);
 
 #ifdef __cplusplus
 }

@@ -12,9 +12,14 @@
 // One thread per output pixel (3 channels); a batch of B frames of one size in one launch.  Input:
 // uint8 [B][H][W][3] BGR (packed rows).  Outputs: uint8 [B][oh][ow][3] BGR (the letterboxed frame,
 // letterbox()'s return), or fp16 / fp32 [B][3][oh][ow] RGB in [0, 1] (the model input).
+// letterbox_ragged_kernel does the same for B frames of B different sizes, each with its own geometry.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+
+#include <algorithm>
+
+#include "yv7_kernels.h"
 
 namespace yv7 {
 
@@ -118,7 +123,125 @@ __global__ void letterbox_kernel(const uint8_t* __restrict__ src, int H, int W, 
   }
 }
 
+// ---- ragged batch: every frame its own size, geometry and resize mode (autoShape, common.py:899-918; a
+// detect.py loop over a directory).  Up to RAGGED_CHUNK frame records travel by value as one kernel argument,
+// so the call needs no host-to-device copy and no workspace; blockIdx.z picks the record, which makes the
+// mode branch uniform per block.  The two coefficient pairs lb_tables_kernel would store are computed inline
+// with the same expressions (the row pair is the same for a whole block); the host supplies each axis'
+// scale = 1.0 / ((double)dst / src) as a double.
+struct LbFrame {
+  const uint8_t* src;
+  double sx, sy;   // column / row scale
+  int H, W, nh, nw, top, left, mode, reserved;
+};
+static_assert(sizeof(LbFrame) == 56, "LbFrame is sized for 64 records in one kernel argument");
+
+struct LbChunk {
+  LbFrame f[RAGGED_CHUNK];
+};
+
+template <int OUT>
+__global__ void letterbox_ragged_kernel(LbChunk ch, int b0, int oh, int ow, uint8_t p0, uint8_t p1, uint8_t p2,
+                                        int swap_rb, void* __restrict__ dst) {
+  const int ox = blockIdx.x * blockDim.x + threadIdx.x;
+  const int oy = blockIdx.y;
+  const LbFrame& f = ch.f[blockIdx.z];
+  const int b = b0 + blockIdx.z;
+  if (ox >= ow) return;
+  const int H = f.H, W = f.W, nw = f.nw;
+  const int y = oy - f.top, x = ox - f.left;
+  int v[3];
+  if ((unsigned)y < (unsigned)f.nh && (unsigned)x < (unsigned)nw) {
+    const uint8_t* img = f.src;
+    if (f.mode == 0) {
+      const uint8_t* p = img + ((size_t)y * W + x) * 3;
+      v[0] = p[0]; v[1] = p[1]; v[2] = p[2];
+    } else if (f.mode == 2) {
+      const uint8_t* q0 = img + ((size_t)(2 * y) * W + 2 * x) * 3;
+      const uint8_t* q1 = q0 + (size_t)W * 3;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) v[c] = (q0[c] + q0[3 + c] + q1[c] + q1[3 + c] + 2) >> 2;
+    } else {
+      // columns: (sx, fx) reset at the borders; rows: fy kept, fetched rows clamped (lb_tables_kernel)
+      float fx = (float)((x + 0.5) * f.sx - 0.5);
+      int s = (int)floorf(fx);
+      fx -= (float)s;
+      if (s < 0) { s = 0; fx = 0.f; }
+      if (s >= W - 1) { s = W - 1; fx = 0.f; }
+      const int sx0 = s * 3, sx1 = min(s + 1, W - 1) * 3;
+      const int a0 = cv_round((1.f - fx) * (float)COEF), a1 = cv_round(fx * (float)COEF);
+      float fy = (float)((y + 0.5) * f.sy - 0.5);
+      const int r = (int)floorf(fy);
+      fy -= (float)r;
+      const uint8_t* r0 = img + (size_t)min(max(r, 0), H - 1) * W * 3;
+      const uint8_t* r1 = img + (size_t)min(max(r + 1, 0), H - 1) * W * 3;
+      const int c0 = cv_round((1.f - fy) * (float)COEF), c1 = cv_round(fy * (float)COEF);
+      const int nv = nw * 3 / SIMD_LANES * SIMD_LANES;   // this frame's SIMD-covered row positions
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const int d0 = r0[sx0 + c] * a0 + r0[sx1 + c] * a1;
+        const int d1 = r1[sx0 + c] * a0 + r1[sx1 + c] * a1;
+        int o;
+        if (x * 3 + c < nv) o = ((((d0 >> 4) * c0) >> 16) + (((d1 >> 4) * c1) >> 16) + 2) >> 2;
+        else o = (d0 * c0 + d1 * c1 + (1 << 21)) >> 22;
+        v[c] = min(max(o, 0), 255);
+      }
+    }
+  } else {
+    v[0] = p0; v[1] = p1; v[2] = p2;
+  }
+  if constexpr (OUT == 0) {
+    uint8_t* d = reinterpret_cast<uint8_t*>(dst) + (((size_t)b * oh + oy) * ow + ox) * 3;
+    d[0] = (uint8_t)v[0]; d[1] = (uint8_t)v[1]; d[2] = (uint8_t)v[2];
+  } else {
+    // planes in the input's channel order, or reversed (BGR frames -> RGB planes) with swap_rb
+    const size_t plane = (size_t)oh * ow, o = (size_t)b * 3 * plane + (size_t)oy * ow + ox;
+    const float f0 = (float)v[0] / 255.0f, f1 = (float)v[1] / 255.0f, f2 = (float)v[2] / 255.0f;
+    const float lo = swap_rb ? f2 : f0, hi = swap_rb ? f0 : f2;
+    if constexpr (OUT == 1) {
+      _Float16* d = reinterpret_cast<_Float16*>(dst);
+      d[o] = (_Float16)lo; d[o + plane] = (_Float16)f1; d[o + 2 * plane] = (_Float16)hi;
+    } else {
+      float* d = reinterpret_cast<float*>(dst);
+      d[o] = lo; d[o + plane] = f1; d[o + 2 * plane] = hi;
+    }
+  }
+}
+
 }  // namespace
+
+hipError_t launch_letterbox_ragged(const RaggedFrame* frames, int B, int oh, int ow, const uint8_t pad[3],
+                                   int swap_rb, int out_kind, void* dst, hipStream_t st) {
+  for (int b0 = 0; b0 < B; b0 += RAGGED_CHUNK) {
+    const int n = std::min(RAGGED_CHUNK, B - b0);
+    LbChunk ch;
+    for (int i = 0; i < RAGGED_CHUNK; ++i) {
+      const RaggedFrame& r = frames[b0 + std::min(i, n - 1)];   // unused records repeat the last one
+      LbFrame& f = ch.f[i];
+      f.src = r.src;
+      f.H = r.H; f.W = r.W; f.nh = r.nh; f.nw = r.nw; f.top = r.top; f.left = r.left;
+      f.sx = 1.0 / ((double)r.nw / r.W);
+      f.sy = 1.0 / ((double)r.nh / r.H);
+      f.mode = 1;
+      if (r.nh == r.H && r.nw == r.W) f.mode = 0;
+      else if (r.W == 2 * r.nw && r.H == 2 * r.nh) f.mode = 2;
+      f.reserved = 0;
+    }
+    const dim3 grid((ow + 127) / 128, oh, n);
+    if (out_kind == 0)
+      hipLaunchKernelGGL(letterbox_ragged_kernel<0>, grid, dim3(128), 0, st, ch, b0, oh, ow, pad[0], pad[1], pad[2],
+                         swap_rb, dst);
+    else if (out_kind == 1)
+      hipLaunchKernelGGL(letterbox_ragged_kernel<1>, grid, dim3(128), 0, st, ch, b0, oh, ow, pad[0], pad[1], pad[2],
+                         swap_rb, dst);
+    else
+      hipLaunchKernelGGL(letterbox_ragged_kernel<2>, grid, dim3(128), 0, st, ch, b0, oh, ow, pad[0], pad[1], pad[2],
+                         swap_rb, dst);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
 
 size_t letterbox_workspace_bytes(int nh, int nw) { return (size_t)(4 * nw + 4 * nh) * sizeof(int) + 256; }
 

@@ -1,5 +1,8 @@
 // libyv7 runtime: the C ABI of include/yv7.h outside the plan — version and error reporting, NMS, the
-// End2End output mode and the letterbox.  (Plans: plan_create.cpp, plan_layout.cpp, forward.cpp.)
+// End2End output mode, the letterbox (one size or ragged) and the boxes' way back to image pixels.
+// (Plans: plan_create.cpp, plan_layout.cpp, forward.cpp.)
+#include <cmath>
+
 #include "plan.h"
 
 using namespace yv7rt;
@@ -110,6 +113,59 @@ int yv7_letterbox(const void* src, int B, int H, int W, int new_h, int new_w, in
   hipError_t e = yv7::launch_letterbox(reinterpret_cast<const uint8_t*>(src), B, H, W, new_h, new_w, top, left, out_h,
                                        out_w, pad, out_kind, dst, workspace, reinterpret_cast<hipStream_t>(stream));
   if (e != hipSuccess) return hip_fail(e, "yv7_letterbox launch");
+  return 0;
+}
+
+static_assert(sizeof(yv7_frame_desc) == sizeof(yv7::RaggedFrame) && sizeof(yv7_scale_desc) == sizeof(yv7::ScaleImage),
+              "the kernels' records mirror the ABI descriptors");
+
+size_t yv7_letterbox_ragged_workspace_bytes(const yv7_frame_desc* frames, int B) {
+  (void)frames;
+  (void)B;
+  return 0;   // the resize coefficients are computed inline: no tables to hold
+}
+
+int yv7_letterbox_ragged(const yv7_frame_desc* frames, int B, int out_h, int out_w, int pad0, int pad1, int pad2,
+                         int swap_rb, int out_kind, void* dst, void* workspace, size_t ws_bytes, void* stream) {
+  if (!frames || !dst) return fail(YV7_E_ARG, "yv7_letterbox_ragged: null argument");
+  if (B <= 0) return fail(YV7_E_ARG, "yv7_letterbox_ragged: B must be positive");
+  if (out_kind < 0 || out_kind > 2) return fail(YV7_E_ARG, "yv7_letterbox_ragged: out_kind must be 0, 1 or 2");
+  if (out_h <= 0 || out_w <= 0 || out_h > 65535)
+    return fail(YV7_E_SHAPE, "yv7_letterbox_ragged: canvas must be positive and at most 65535 rows");
+  for (int v : {pad0, pad1, pad2})
+    if (v < 0 || v > 255) return fail(YV7_E_ARG, "yv7_letterbox_ragged: pad colour outside 0..255");
+  for (int i = 0; i < B; ++i) {
+    const yv7_frame_desc& f = frames[i];
+    const std::string who = "yv7_letterbox_ragged: frame " + std::to_string(i);
+    if (!f.data) return fail(YV7_E_ARG, who + " has null data");
+    if (f.h <= 0 || f.w <= 0 || f.new_h <= 0 || f.new_w <= 0) return fail(YV7_E_SHAPE, who + " has a non-positive size");
+    if (f.top < 0 || f.left < 0 || (int64_t)f.top + f.new_h > out_h || (int64_t)f.left + f.new_w > out_w)
+      return fail(YV7_E_SHAPE, who + ": the resized image must lie inside the output canvas");
+    if ((size_t)f.h * f.w * 3 >= ((size_t)1 << 40)) return fail(YV7_E_SHAPE, who + " is too large");
+  }
+  if (ws_bytes < yv7_letterbox_ragged_workspace_bytes(frames, B) || (ws_bytes > 0 && !workspace))
+    return fail(YV7_E_WORKSPACE, "yv7_letterbox_ragged: workspace null or too small");
+  const uint8_t pad[3] = {(uint8_t)pad0, (uint8_t)pad1, (uint8_t)pad2};
+  hipError_t e = yv7::launch_letterbox_ragged(reinterpret_cast<const yv7::RaggedFrame*>(frames), B, out_h, out_w, pad,
+                                              swap_rb != 0, out_kind, dst, reinterpret_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return hip_fail(e, "yv7_letterbox_ragged launch");
+  return 0;
+}
+
+int yv7_scale_boxes(float* det, const int32_t* count, int B, int max_det, const yv7_scale_desc* images,
+                    int round_boxes, float* xywh, float* xyxyn, float* xywhn, void* stream) {
+  if (!det || !count || !images) return fail(YV7_E_ARG, "yv7_scale_boxes: null argument");
+  if (B <= 0) return fail(YV7_E_ARG, "yv7_scale_boxes: B must be positive");
+  if (max_det <= 0) return fail(YV7_E_ARG, "yv7_scale_boxes: max_det must be positive");
+  for (int i = 0; i < B; ++i) {
+    const std::string who = "yv7_scale_boxes: image " + std::to_string(i);
+    if (images[i].h0 <= 0 || images[i].w0 <= 0) return fail(YV7_E_SHAPE, who + " has a non-positive size");
+    if (!(images[i].gain > 0.f) || !std::isfinite(images[i].gain))
+      return fail(YV7_E_ARG, who + ": gain must be positive and finite");
+  }
+  hipError_t e = yv7::launch_scale_boxes(det, count, B, max_det, reinterpret_cast<const yv7::ScaleImage*>(images),
+                                         round_boxes != 0, xywh, xyxyn, xywhn, reinterpret_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return hip_fail(e, "yv7_scale_boxes launch");
   return 0;
 }
 

@@ -322,6 +322,22 @@ hipError_t launch_row_best(const float* z, int B, int N, int no, void* rowbest, 
 size_t letterbox_workspace_bytes(int nh, int nw);
 hipError_t launch_letterbox(const uint8_t* src, int B, int H, int W, int nh, int nw, int top, int left, int oh,
                             int ow, const uint8_t pad[3], int out_kind, void* dst, void* ws, hipStream_t st);
+// Ragged batches: per-frame / per-image records reach the kernels by value, RAGGED_CHUNK per launch (a kernel
+// argument block holds 4 KiB).  RaggedFrame and ScaleImage have the layouts of yv7_frame_desc / yv7_scale_desc.
+constexpr int RAGGED_CHUNK = 64;
+struct RaggedFrame {
+  const uint8_t* src;
+  int32_t H, W, nh, nw, top, left;
+};
+struct ScaleImage {
+  int32_t h0, w0;
+  float gain, pad_w, pad_h;
+};
+hipError_t launch_letterbox_ragged(const RaggedFrame* frames, int B, int oh, int ow, const uint8_t pad[3],
+                                   int swap_rb, int out_kind, void* dst, hipStream_t st);
+// postprocess.hip
+hipError_t launch_scale_boxes(float* det, const int32_t* count, int B, int max_det, const ScaleImage* images,
+                              int round_boxes, float* xywh, float* xyxyn, float* xywhn, hipStream_t st);
 hipError_t launch_end2end_pack(const float* det, const int32_t* count, int B, int max_det, int topk,
                                int32_t* num_dets, float* boxes, float* scores, int32_t* classes, hipStream_t st);
 

@@ -7,6 +7,10 @@ unpinned), there are no checkpoints offline so `--cfg NAME --synthetic-seed S` b
 weights instead of `--weights`, and drawing/saving annotated images (utils/plots.py, cv2) is out of
 scope — `--save-txt` writes the reference's label format.  There is no CPU execution path.
 
+`--batch-size N` (N > 1) runs groups of up to N files, of whatever sizes, per forward: one ragged letterbox
+launch (yv7_letterbox_ragged), one forward, one batched NMS, one box-scaling launch (yv7_scale_boxes with the
+.round()); the default, 1, is the reference's loop above.
+
     python detect.py --cfg yolov7-tiny --source ../tests/golden/bus.jpg --img-size 640
 """
 from __future__ import annotations
@@ -22,8 +26,10 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import torch  # noqa: E402
 
 from models.experimental import attempt_load  # noqa: E402
-from utils.datasets import LoadImages  # noqa: E402
-from utils.general import check_img_size, non_max_suppression, scale_coords, xyxy2xywh  # noqa: E402
+from utils.datasets import (OUT_F16_CHW, OUT_F32_CHW, LoadImages, imread, letterbox_geometry,  # noqa: E402
+                            letterbox_ragged)
+from utils.general import (check_img_size, nms_batched, non_max_suppression, scale_boxes, scale_coords,  # noqa: E402
+                           scale_desc, xyxy2xywh)
 from utils.torch_utils import select_device, time_synchronized  # noqa: E402
 
 
@@ -35,6 +41,44 @@ def load_model(opt, device):
     m = Model(opt.cfg or 'yolov7')
     synthetic_state_dict(m, seed=opt.synthetic_seed)
     return attempt_load(m, map_location=device)
+
+
+def detect_batched(opt, model, dataset, imgsz, half, names, save_dir):
+    """The loop of detect() over groups of up to opt.batch_size files, each group one forward."""
+    device = next(model.parameters()).device
+    results = []
+    files = dataset.files
+    for g0 in range(0, len(files), opt.batch_size):
+        paths = files[g0:g0 + opt.batch_size]
+        im0s = [imread(p) for p in paths]                  # BGR, sizes may differ
+        geoms = [letterbox_geometry(im0.shape[:2], (imgsz, imgsz), auto=False) for im0 in im0s]   # datasets.py:196
+        t1 = time_synchronized()
+        img = letterbox_ragged(im0s, geoms, (imgsz, imgsz), swap_rb=True, device=device,
+                               out_kind=OUT_F16_CHW if half else OUT_F32_CHW)
+        with torch.no_grad():
+            pred = model(img, augment=opt.augment)[0]
+        t2 = time_synchronized()
+        det, _, cnt = nms_batched(pred, opt.conf_thres, opt.iou_thres, classes=opt.classes, agnostic=opt.agnostic_nms)
+        scale_boxes(det, cnt, [scale_desc(img.shape[2:], im0.shape) for im0 in im0s], round_boxes=True, views=False)
+        counts = cnt.tolist()
+        t3 = time_synchronized()
+        for i, (path, im0) in enumerate(zip(paths, im0s)):
+            d, s = det[i, :counts[i]].cpu(), ''
+            gn = torch.tensor(im0.shape)[[1, 0, 1, 0]]      # normalization gain whwh
+            for c in d[:, -1].unique():
+                n = (d[:, -1] == c).sum()
+                s += f"{n} {names[int(c)]}{'s' * (n > 1)}, "
+            if opt.save_txt and len(d):
+                with open(save_dir / 'labels' / (Path(path).stem + '.txt'), 'a') as f:
+                    for *xyxy, conf, cls in reversed(d):
+                        xywh = (xyxy2xywh(torch.tensor(xyxy).view(1, 4)) / gn).view(-1).tolist()
+                        line = (cls, *xywh, conf) if opt.save_conf else (cls, *xywh)
+                        f.write(('%g ' * len(line)).rstrip() % line + '\n')
+            if not opt.quiet:
+                print(f'{s}Done. ({(1E3 * (t2 - t1) / len(paths)):.1f}ms) Inference, '
+                      f'({(1E3 * (t3 - t2) / len(paths)):.1f}ms) NMS')
+            results.append((path, d))
+    return results
 
 
 def detect(opt):
@@ -56,6 +100,11 @@ def detect(opt):
         (save_dir / 'labels').mkdir(parents=True, exist_ok=True)
     results = []
     t0 = time.time()
+    if opt.batch_size > 1:
+        results = detect_batched(opt, model, dataset, imgsz, half, names, save_dir)
+        if not opt.quiet:
+            print(f'Done. ({time.time() - t0:.3f}s)')
+        return results
     for path, img, im0s, vid_cap, ratio, dwdh in dataset:
         img = torch.from_numpy(img).to(device)
         img = img.half() if half else img.float()          # uint8 to fp16/32
@@ -109,6 +158,7 @@ def parse_opt(argv=None):
     ap.add_argument('--project', default='runs/detect', help='save results to project/name')
     ap.add_argument('--name', default='exp', help='save results to project/name')
     ap.add_argument('--fp32', action='store_true', help='run the fp32 plan instead of half()')
+    ap.add_argument('--batch-size', type=int, default=1, help='files per forward (sizes may differ); 1 = one by one')
     ap.add_argument('--quiet', action='store_true')
     return ap.parse_args(argv)
 

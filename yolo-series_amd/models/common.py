@@ -7,16 +7,28 @@ rbr_identity, rbr_reparam, cv1..cv7, m, mp, d, implicit) are identical, so refer
 whole network runs on the MI355X through the compiled plan (yv7.graph / libyv7), never layer by
 layer and never on the CPU, so calling a layer directly raises.
 
+The model's front door for real images is here too (common.py:852-1012): NMS, autoShape ("a list of images
+of whatever size in, boxes in each image's own pixels out") and its result class Detections.  autoShape runs one
+ragged letterbox launch, one forward, one batched NMS and one box-scaling launch per call (libyv7
+yv7_letterbox_ragged / yv7_nms / yv7_scale_boxes); drawing (show / save / render, utils/plots.py) and URL
+inputs are out of scope.
+
 Folding (Model.fuse in the reference) is restated here with the reference arithmetic:
   Conv:    fuse_conv_and_bn      utils/torch_utils.py:181-201
   RepConv: fuse_repvgg_block     models/common.py:584-643 (+ fuse_conv_bn 561-582)
 """
 from __future__ import annotations
 
+from copy import copy
+from pathlib import Path
+
+import numpy as np
 import torch
 import torch.nn as nn
 
-from utils.torch_utils import fuse_conv_and_bn
+from utils.datasets import OUT_F16_CHW, OUT_F32_CHW, autoshape_geometry, letterbox_ragged
+from utils.general import nms_batched, non_max_suppression, scale_boxes, xyxy2xywh
+from utils.torch_utils import fuse_conv_and_bn, time_synchronized
 
 
 def autopad(k, p=None):  # models/common.py:23-27
@@ -200,3 +212,156 @@ class ImplicitM(_PlanOnly):  # common.py:446-456
         self.std = std
         self.implicit = nn.Parameter(torch.ones(1, channel, 1, 1))
         nn.init.normal_(self.implicit, mean=self.mean, std=self.std)
+
+
+class NMS(nn.Module):  # common.py:852-862
+    conf = 0.25     # confidence threshold
+    iou = 0.45      # IoU threshold
+    classes = None  # (optional list) filter by class
+
+    def forward(self, x):
+        return non_max_suppression(x[0], conf_thres=self.conf, iou_thres=self.iou, classes=self.classes)
+
+
+def _as_hwc3(im):
+    """common.py:906-908 on one decoded image: CHW -> HWC when shape[0] < 5, alpha dropped, grey tiled to 3."""
+    is_u8 = (isinstance(im, np.ndarray) and im.dtype == np.uint8) or \
+            (isinstance(im, torch.Tensor) and im.dtype == torch.uint8)
+    if not is_u8:
+        raise ValueError(f'autoShape: images must be uint8 (got {getattr(im, "dtype", type(im).__name__)}); '
+                         f'scale and convert before the call')
+    if isinstance(im, torch.Tensor):
+        if not im.is_cuda or im.ndim != 3 or im.shape[2] != 3:
+            raise ValueError(f'autoShape: a tensor image must be uint8 [H, W, 3] on the HIP device, got '
+                             f'{tuple(im.shape)} on {im.device}')
+        return im
+    if im.ndim not in (2, 3):
+        raise ValueError(f'autoShape: expected an HWC, CHW or HW image, got shape {im.shape}')
+    if im.shape[0] < 5:
+        im = im.transpose((1, 2, 0))
+    return im[:, :, :3] if im.ndim == 3 else np.tile(im[:, :, None], 3)
+
+
+class autoShape(nn.Module):  # common.py:865-932
+    """Input-robust model wrapper: filenames, PIL images, uint8 numpy arrays (HWC / CHW / HW) or uint8 HWC HIP
+    tensors, one or a list, any sizes, RGB -> Detections.  A float tensor goes straight to the model."""
+    conf = 0.25     # NMS confidence threshold
+    iou = 0.45      # NMS IoU threshold
+    classes = None  # (optional list) filter by class
+
+    def __init__(self, model):
+        super().__init__()
+        self.model = model.eval()
+
+    def autoshape(self):
+        print('autoShape already enabled, skipping... ')
+        return self
+
+    @torch.no_grad()
+    def forward(self, imgs, size=640, augment=False, profile=False):
+        t = [time_synchronized()]
+        p = next(self.model.parameters())   # for device and type
+        if isinstance(imgs, torch.Tensor):
+            return self.model(imgs.to(p.device).type_as(p), augment, profile)
+        if p.device.type != 'cuda':
+            raise RuntimeError('autoShape runs on a ROCm (MI355X) device via libyv7; move the model to cuda')
+
+        n, imgs = (len(imgs), list(imgs)) if isinstance(imgs, (list, tuple)) else (1, [imgs])
+        files = []
+        for i, im in enumerate(imgs):
+            f = f'image{i}'
+            if isinstance(im, (str, Path)):
+                from PIL import Image
+                if str(im).startswith('http'):
+                    raise ValueError('autoShape: URLs are not supported (this package has no network code)')
+                with Image.open(im) as pil:
+                    im, f = np.asarray(pil.convert('RGB')), str(im)
+            elif hasattr(im, 'convert') and hasattr(im, 'size'):   # PIL Image
+                im, f = np.asarray(im), getattr(im, 'filename', f) or f
+            files.append(Path(f).with_suffix('.jpg').name)
+            imgs[i] = _as_hwc3(im)
+        shape0 = [tuple(im.shape[:2]) for im in imgs]
+        shape1, geoms, descs = autoshape_geometry(shape0, size, int(self.stride.max()))
+        x = letterbox_ragged(imgs, geoms, shape1, swap_rb=False, device=p.device,
+                             out_kind=OUT_F16_CHW if p.dtype == torch.float16 else OUT_F32_CHW)
+        t.append(time_synchronized())
+
+        y = self.model(x, augment, profile)[0]
+        t.append(time_synchronized())
+
+        det, _, cnt = nms_batched(y, conf_thres=self.conf, iou_thres=self.iou, classes=self.classes)
+        views = scale_boxes(det, cnt, descs, round_boxes=False, views=True)
+        counts = cnt.tolist()   # the one host sync: variable-length outputs
+        pred, xywh, xyxyn, xywhn = ([v[i, :c] for i, c in enumerate(counts)] for v in (det, *views))
+        t.append(time_synchronized())
+        return Detections(imgs, pred, files, t, self.names, x.shape, views=(xywh, xyxyn, xywhn))
+
+
+class Detections:  # common.py:935-1012
+    """Results of one autoShape call: per image pred = xyxy [n, 6] (x1, y1, x2, y2, conf, cls) in the image's own
+    pixels, and the views xywh (centre, size), xyxyn, xywhn (normalised by the image's w, h)."""
+
+    def __init__(self, imgs, pred, files, times=None, names=None, shape=None, views=None):
+        self.imgs = imgs      # list of images as given (numpy arrays or HIP tensors, HWC)
+        self.pred = pred      # list of tensors pred[0] = (xyxy, conf, cls)
+        self.names = names    # class names
+        self.files = files    # image filenames
+        self.xyxy = pred
+        if views is None:     # common.py:940-948 in tensor math, for results assembled by hand
+            gn = [torch.tensor([*[im.shape[i] for i in (1, 0, 1, 0)], 1., 1.], device=x.device)
+                  for im, x in zip(imgs, pred)]
+            xywh = [xyxy2xywh(x) for x in pred]
+            views = xywh, [x / g for x, g in zip(pred, gn)], [x / g for x, g in zip(xywh, gn)]
+        self.xywh, self.xyxyn, self.xywhn = views
+        self.n = len(self.pred)   # number of images (batch size)
+        self.t = tuple((times[i + 1] - times[i]) * 1000 / self.n for i in range(3)) if times else (0., 0., 0.)
+        self.s = shape            # inference BCHW shape
+
+    def _summary(self, i):
+        """display()'s line for image i: 'image 1/2: 1080x810 4 persons, 1 bus'."""
+        img, pred = self.imgs[i], self.pred[i]
+        line = f'image {i + 1}/{self.n}: {img.shape[0]}x{img.shape[1]} '
+        for c in pred[:, -1].unique():
+            k = int((pred[:, -1] == c).sum())   # detections per class
+            line += f"{k} {self.names[int(c)]}{'s' * (k > 1)}, "
+        return line.rstrip(', ')
+
+    def print(self):
+        for i in range(self.n):
+            print(self._summary(i))
+        print(f'Speed: %.1fms pre-process, %.1fms inference, %.1fms NMS per image at shape {tuple(self.s)}' % self.t)
+
+    def show(self):
+        raise NotImplementedError('Detections.show: drawing (utils/plots.py) is not part of this package')
+
+    def save(self, save_dir='runs/hub/exp'):
+        raise NotImplementedError('Detections.save: drawing (utils/plots.py) is not part of this package')
+
+    def render(self):
+        raise NotImplementedError('Detections.render: drawing (utils/plots.py) is not part of this package')
+
+    def pandas(self):
+        """A copy whose four views are pandas DataFrames, i.e. print(results.pandas().xyxy[0])."""
+        import pandas as pd
+        new = copy(self)
+        ca = 'xmin', 'ymin', 'xmax', 'ymax', 'confidence', 'class', 'name'
+        cb = 'xcenter', 'ycenter', 'width', 'height', 'confidence', 'class', 'name'
+        for k, cols in zip(('xyxy', 'xyxyn', 'xywh', 'xywhn'), (ca, ca, cb, cb)):
+            rows = [[r[:5] + [int(r[5]), self.names[int(r[5])]] for r in x.tolist()] for x in getattr(self, k)]
+            setattr(new, k, [pd.DataFrame(r, columns=cols) for r in rows])
+        return new
+
+    def tolist(self):
+        """One Detections per image, its list fields unwrapped, i.e. 'for result in results.tolist():'."""
+        out = []
+        for i in range(self.n):
+            d = Detections([self.imgs[i]], [self.pred[i]], [self.files[i]], None, self.names, self.s,
+                           views=([self.xywh[i]], [self.xyxyn[i]], [self.xywhn[i]]))
+            d.t = self.t
+            for k in ('imgs', 'pred', 'xyxy', 'xyxyn', 'xywh', 'xywhn'):
+                setattr(d, k, getattr(d, k)[0])   # pop out of list
+            out.append(d)
+        return out
+
+    def __len__(self):
+        return self.n

@@ -6,6 +6,7 @@ Same names, constructor arguments, attributes and return values as the reference
                                   initialize_weights)
   Model.forward(x, augment, profile) -> (z [B,N,no], xs list of [B,na,ny,nx,no])   yolo.py:581-631
   Model.fuse()                    yolo.py:693-710
+  Model.autoshape()               yolo.py:726-730 (models.common.autoShape around this model)
   parse_model(d, ch)              yolo.py:736-813 (module names resolved through a registry, not eval)
 
 What differs is where the work happens: `forward` compiles the (fused) network once per
@@ -25,7 +26,8 @@ from pathlib import Path
 import torch
 import torch.nn as nn
 
-from models.common import (MP, SP, Concat, Conv, DownC, ImplicitA, ImplicitM, ReOrg, RepConv, Shortcut, SPPCSPC)
+from models.common import (MP, SP, Concat, Conv, DownC, ImplicitA, ImplicitM, ReOrg, RepConv, Shortcut, SPPCSPC,
+                           autoShape)
 from utils.general import make_divisible
 from utils.torch_utils import initialize_weights, model_info, scale_img
 
@@ -294,6 +296,14 @@ class Model(nn.Module):
         self._plans = {}
         self.info()
         return self
+
+    def autoshape(self):  # yolo.py:726-730
+        print('Adding autoShape... ')
+        m = autoShape(self)   # wrap model
+        for k in ('yaml', 'nc', 'hyp', 'names', 'stride'):   # copy_attr(include=...): the attributes that exist
+            if k in self.__dict__:
+                setattr(m, k, self.__dict__[k])
+        return m
 
     def info(self, verbose=False, img_size=640):
         model_info(self, verbose, img_size)

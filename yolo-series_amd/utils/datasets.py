@@ -5,7 +5,9 @@ value of utils/datasets.py:1277-1307 ((img, ratio, (dw, dh)); img HWC BGR uint8)
 border done by libyv7 (yv7_letterbox: cv2.resize INTER_LINEAR restated bit for bit in fixed point,
 see csrc/preprocess.hip).  `letterbox_batch(frames, img_size, half, ...)` fuses it with detect.py's
 conversion (img[:, :, ::-1].transpose(2, 0, 1), .half()/.float(), /= 255, detect.py:100-104) and
-writes the [B, 3, S, S] model input in one launch.  There is no CPU path: inputs go to the current
+writes the [B, 3, S, S] model input in one launch; `letterbox_ragged(frames, geoms, canvas, ...)` does
+so for frames of different sizes (yv7_letterbox_ragged), with `autoshape_geometry` supplying autoShape's
+inference shape and per-frame geometry (models/common.py:909-915).  There is no CPU path: inputs go to the current
 HIP device and the library must be built (the ctypes binding raises otherwise).
 """
 from __future__ import annotations
@@ -13,6 +15,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from utils.general import make_divisible, scale_desc
 from yv7 import _lib as L
 
 OUT_U8_HWC, OUT_F16_CHW, OUT_F32_CHW = 0, 1, 2
@@ -92,6 +95,72 @@ def letterbox_batch(frames, img_size=640, half=True, color=(114, 114, 114), auto
     geom = letterbox_geometry(tuple(frames.shape[1:3]), img_size, auto, scaleFill, scaleup, stride)
     x = _run(frames, geom, color, OUT_F16_CHW if half else OUT_F32_CHW)
     return x, geom[1], geom[2]
+
+
+def autoshape_geometry(shapes, size=640, stride=32):
+    """autoShape's shapes (common.py:909-915) for frames of `shapes` [(h, w), ...]: the common inference
+    shape shape1 = [h1, w1] (every frame scaled so its longer side is `size`, the per-axis maximum rounded
+    up to `stride` — in Python floats, whose rounding is part of the result: 147 * (640 / 147) > 640), each
+    frame's letterbox_geometry(shape, shape1, auto=False) and each frame's scale_desc(shape1, shape)."""
+    shape1 = [[y * (size / max(s)) for y in s] for s in shapes]
+    shape1 = [make_divisible(max(s[k] for s in shape1), int(stride)) for k in (0, 1)]
+    geoms = [letterbox_geometry(tuple(s), shape1, auto=False) for s in shapes]
+    return shape1, geoms, [scale_desc(shape1, s) for s in shapes]
+
+
+def _hip_device(device):
+    device = torch.device(device)
+    return torch.device('cuda', torch.cuda.current_device()) if device.index is None else device
+
+
+def pack_frames(frames, device):
+    """A list of uint8 HWC frames (numpy arrays or HIP tensors) -> (device pointers, the tensors behind
+    them).  Host frames travel in one packed buffer, one host-to-device copy; HIP tensors are used in place."""
+    host = [(i, np.ascontiguousarray(f)) for i, f in enumerate(frames) if isinstance(f, np.ndarray)]
+    ptrs, keep = [None] * len(frames), []
+    if host:
+        packed = torch.from_numpy(np.concatenate([f.reshape(-1) for _, f in host])).to(device)
+        keep.append(packed)
+        off = 0
+        for i, f in host:
+            ptrs[i] = packed.data_ptr() + off
+            off += f.size
+    for i, f in enumerate(frames):
+        if isinstance(f, torch.Tensor):
+            if f.device != device:
+                raise RuntimeError(f'letterbox_ragged: tensor frames must be on {device}, got {f.device}')
+            f = f.contiguous()
+            keep.append(f)
+            ptrs[i] = f.data_ptr()
+    return ptrs, keep
+
+
+def letterbox_ragged(frames, geoms, canvas, color=(114, 114, 114), swap_rb=False, out_kind=OUT_F32_CHW,
+                     device=None):
+    """One yv7_letterbox_ragged call: frames (uint8 HWC numpy arrays or HIP tensors, any sizes) with their
+    letterbox_geometry results onto a canvas (h, w) -> [B, h, w, 3] uint8 or [B, 3, h, w] half / float in
+    [0, 1].  color is in the frames' channel order; swap_rb reverses the channel order of the float outputs."""
+    device = _hip_device(device if device is not None else 'cuda')
+    for f in frames:
+        u8 = f.dtype == (torch.uint8 if isinstance(f, torch.Tensor) else np.uint8)
+        if not u8 or f.ndim != 3 or f.shape[2] != 3:
+            raise ValueError(f'letterbox_ragged: expected uint8 [H, W, 3] frames, got {f.dtype} {tuple(f.shape)}')
+    B, (oh, ow) = len(frames), canvas
+    ptrs, keep = pack_frames(frames, device)   # `keep` lives until the launch below is enqueued on the stream
+    descs = (L.FrameDesc * B)()
+    for d, p, f, ((nw, nh), _, _, (top, _, left, _)) in zip(descs, ptrs, frames, geoms):
+        d.data, d.h, d.w, d.new_h, d.new_w, d.top, d.left = p, f.shape[0], f.shape[1], nh, nw, top, left
+    if out_kind == OUT_U8_HWC:
+        out = torch.empty((B, oh, ow, 3), dtype=torch.uint8, device=device)
+    else:
+        out = torch.empty((B, 3, oh, ow), dtype=torch.float16 if out_kind == OUT_F16_CHW else torch.float32,
+                          device=device)
+    c = [int(v) for v in color]
+    with torch.cuda.device(device):
+        stream = torch.cuda.current_stream(device).cuda_stream
+        L.check(L.lib().yv7_letterbox_ragged(descs, B, oh, ow, c[0], c[1], c[2], int(bool(swap_rb)), out_kind,
+                                             out.data_ptr(), None, 0, stream), 'yv7_letterbox_ragged')
+    return out
 
 
 # ------------------------------------------------------------------------------------------ images

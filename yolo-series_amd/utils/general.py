@@ -70,6 +70,37 @@ def scale_coords(img1_shape, coords, img0_shape, ratio_pad=None):  # general.py:
     return coords
 
 
+def scale_desc(img1_shape, img0_shape):
+    """The scalars of scale_coords(img1_shape, ., img0_shape) (general.py:342-343) as yv7_scale_desc
+    values (h0, w0, gain, pad_w, pad_h): Python floats here, narrowed to fp32 once at the C boundary."""
+    h0, w0 = int(img0_shape[0]), int(img0_shape[1])
+    gain = min(img1_shape[0] / h0, img1_shape[1] / w0)
+    return h0, w0, gain, (img1_shape[1] - w0 * gain) / 2, (img1_shape[0] - h0 * gain) / 2
+
+
+def scale_boxes(det, count, descs, round_boxes=False, views=True):
+    """scale_coords + clip_coords (general.py:340-361) on nms_batched's outputs, in place and stream-ordered
+    (libyv7 yv7_scale_boxes): det [B,max_det,6], count [B] int32, descs one scale_desc per image.
+    round_boxes adds detect.py:183's .round().  With views, also returns Detections' (xywh, xyxyn, xywhn)
+    (common.py:946-948), each [B,max_det,6] with rows beyond count[b] zero; otherwise None."""
+    if not det.is_cuda:
+        raise RuntimeError('scale_boxes runs on a ROCm device (libyv7); got a CPU tensor')
+    B, max_det, six = det.shape
+    if det.dtype != torch.float32 or six != 6 or not det.is_contiguous() or len(descs) != B:
+        raise ValueError(f'scale_boxes: expected contiguous fp32 det [B, max_det, 6] and {B} descriptors')
+    if count.dtype != torch.int32 or count.numel() != B:
+        raise ValueError('scale_boxes: count must be int32 [B]')
+    arr = (_lib.ScaleDesc * B)(*[_lib.ScaleDesc(*d) for d in descs])
+    out = tuple(torch.empty_like(det) for _ in range(3)) if views else None
+    ptrs = [t.data_ptr() for t in out] if views else [None] * 3
+    dev = det.device
+    with torch.cuda.device(dev):
+        rc = _lib.lib().yv7_scale_boxes(det.data_ptr(), count.data_ptr(), B, max_det, arr, int(bool(round_boxes)),
+                                        *ptrs, torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(rc, 'yv7_scale_boxes')
+    return out
+
+
 def box_iou(box1, box2):  # general.py:464-486
     def box_area(box):
         return (box[2] - box[0]) * (box[3] - box[1])

@@ -54,6 +54,19 @@ class NetDesc(ctypes.Structure):
                 ('max_shift', ctypes.c_int32)]
 
 
+class FrameDesc(ctypes.Structure):
+    """yv7_frame_desc: one frame of a ragged letterbox batch."""
+    _fields_ = [('data', ctypes.c_void_p), ('h', ctypes.c_int32), ('w', ctypes.c_int32),
+                ('new_h', ctypes.c_int32), ('new_w', ctypes.c_int32), ('top', ctypes.c_int32),
+                ('left', ctypes.c_int32)]
+
+
+class ScaleDesc(ctypes.Structure):
+    """yv7_scale_desc: one image's way back from the canvas to its own pixels."""
+    _fields_ = [('h0', ctypes.c_int32), ('w0', ctypes.c_int32), ('gain', ctypes.c_float),
+                ('pad_w', ctypes.c_float), ('pad_h', ctypes.c_float)]
+
+
 _vp, _i, _i64, _sz, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float
 
 # name -> (restype, argtypes); every symbol include/yv7.h declares
@@ -78,6 +91,9 @@ SIGNATURES = {
     'yv7_end2end': (_i, [_vp, _i, _i, _i, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'yv7_letterbox_workspace_bytes': (_sz, [_i, _i]),
     'yv7_letterbox': (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    'yv7_letterbox_ragged_workspace_bytes': (_sz, [ctypes.POINTER(FrameDesc), _i]),
+    'yv7_letterbox_ragged': (_i, [ctypes.POINTER(FrameDesc), _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    'yv7_scale_boxes': (_i, [_vp, _vp, _i, _i, ctypes.POINTER(ScaleDesc), _i, _vp, _vp, _vp, _vp]),
 }
 
 _LIB = None
