@@ -4,7 +4,8 @@ Executes yv7.graph.compile_model()'s op list with plain torch CPU ops on NHWC fp
 packed weight blob exactly as the HIP runtime does (csrc/plan_layout.cpp and forward.cpp: tensor shapes from `shift`,
 channel slices by offset, weights [cout_pad32][k][k][cin_pad] with K padded to 64).  Comparing its z
 with the oracle's checks the graph compiler — concat placement, SPPCSPC pool cascade, ReOrg / stem
-fusion, sibling-conv merging, detect-row layout — on CPU, independent of the GPU kernels.
+fusion, sibling-conv merging, DownC, Shortcut as ADD or as a conv's residual, detect-row layout — on CPU,
+independent of the GPU kernels.
 """
 from __future__ import annotations
 
@@ -80,6 +81,8 @@ def run(g, x: torch.Tensor, return_tensors=False):
                 w = _weights(blob, g.dtype, o['w_off'], o['cout'], o['k'], o['cin'])
             y = _act(F.conv2d(src, w, _bias(blob, o['b_off'], o['cout']), 1 if o.get('pool', 0) else o['s'],
                               o['pad']), o['act'])
+            if o.get('src2', -1) >= 0:   # a folded Shortcut: the residual joins after the activation, the order of
+                y = y + T[o['src2']][:, o['src2_coff']:o['src2_coff'] + o['cout']]   # csrc/conv_f16_ring.hip's epilogue
             T[o['dst']][:, o['dst_coff']:o['dst_coff'] + o['cout']] = y
         elif kind == L.OP_MAXPOOL:
             src = T[o['src']][:, o['src_coff']:o['src_coff'] + o['cout']]
@@ -88,6 +91,9 @@ def run(g, x: torch.Tensor, return_tensors=False):
         elif kind == L.OP_UPSAMPLE:
             src = T[o['src']][:, o['src_coff']:o['src_coff'] + o['cout']]
             T[o['dst']][:, o['dst_coff']:o['dst_coff'] + o['cout']] = F.interpolate(src, scale_factor=2.0, mode='nearest')
+        elif kind == L.OP_ADD:   # Shortcut (models/common.py Shortcut: x[0] + x[1])
+            a, b = (T[o[k]][:, o[k + '_coff']:o[k + '_coff'] + o['cout']] for k in ('src', 'src2'))
+            T[o['dst']][:, o['dst_coff']:o['dst_coff'] + o['cout']] = a + b
         elif kind == L.OP_COPY:
             T[o['dst']][:, o['dst_coff']:o['dst_coff'] + o['cout']] = T[o['src']][:, o['src_coff']:o['src_coff'] + o['cout']]
         elif kind == L.OP_DETECT:

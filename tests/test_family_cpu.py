@@ -241,6 +241,40 @@ def test_fold_shortcuts_conditions(monkeypatch):
     assert not any('src2' in o for o in g.ops if o['kind'] == L.OP_CONV)
 
 
+@pytest.mark.parametrize('key', [('mini',), ('add', 48), ('res', 64)], ids=['mini', 'add48', 'res64'])
+def test_plan_semantics_of_downc_and_shortcut(key, monkeypatch):
+    """The compiled plans, executed op by op on the CPU (tests/plan_interp.py): the fp32 plan (DownC decomposed,
+    Shortcut as ADD) reproduces family_ref's z to test_graph.py::test_plan_semantics_vs_oracle's tolerance, and the
+    fp16 plan computes the same bits whether its Shortcuts run as ADDs or as the residual of a conv (default rule,
+    all folded, none folded): a folded conv has no sibling in these nets, so no summation order changes.  add_net
+    and res_net put the ADD / the residual at non-zero channel offsets of tensors of different widths."""
+    import family_ref
+    import plan_interp
+    from helpers import frames
+    m = fresh(key)
+    x = frames(2, 32, 32)
+    shortcuts = sum(type(l).__name__ == 'Shortcut' for l in m.model)
+    monkeypatch.delenv('YV7_NO_RESFUSE', raising=False)
+    monkeypatch.delenv('YV7_RESFUSE', raising=False)
+    with torch.no_grad():
+        torch.testing.assert_close(plan_interp.run(compile_model(m, L.DT_F32), x), family_ref.forward(m, x)[0],
+                                   rtol=1e-4, atol=1e-3)
+        split, zs = [], []
+        for knob in (None, 'YV7_RESFUSE', 'YV7_NO_RESFUSE'):
+            if knob:
+                monkeypatch.setenv(knob, '1')
+            g = compile_model(m, L.DT_F16)
+            if knob:
+                monkeypatch.delenv(knob)
+            split.append((sum(o['kind'] == L.OP_CONV and 'src2' in o for o in g.ops),
+                          sum(o['kind'] == L.OP_ADD for o in g.ops)))
+            zs.append(plan_interp.run(g, x))
+    assert all(r + a == shortcuts for r, a in split) and split[2][0] == 0
+    if key == ('mini',):
+        assert split == [(1, 1), (2, 0), (0, 2)]
+    assert torch.equal(zs[0], zs[1]) and torch.equal(zs[0], zs[2])
+
+
 def test_shortcut_of_unequal_inputs_is_rejected():
     from models.yolo import Model
     cfg = copy.deepcopy(MINI_E6E)
