@@ -15,6 +15,12 @@ dispatch a forward took (tile-count dependent kernel choice, split-K, persistent
 Convolutions run as sums of per-tap fp32 matmuls on the device (no MIOpen: nothing is compiled at
 run time).  Tolerances: an fp16 output within one fp16 ulp of the fp32 reference (+1e-4 of the op's
 rms for the accumulation order; two ulps for the fused stem, whose intermediate is fp16); fp32 outputs within 1e-5 |ref| + 1e-4 rms; max / upsample / copy exact.
+An output that is not finite is an element off; a reference that is not finite is an error naming the op's input.
+
+check_ops checks DETECT through the raw logits, and a forward that returns them never runs the persistent heads
+(csrc/conv_det.hip).  check_detect_z checks z alone: per level a float64 conv + decode of the op's own input
+against z's rows, within the bound check_z_level derives from the two tolerances above (raw logits 1e-4 of
+their scale, decode 1e-5).
 """
 from __future__ import annotations
 
@@ -61,19 +67,28 @@ def conv_ref(x, w, b, s, act):
     return _act(y, act).view(B, Ho, Wo, -1)
 
 
-def _ulp_check(got, ref, what, fp16, ulps=1):
+def _ulp_check(got, ref, what, fp16, ulps=1, xin=None):
+    """A non-finite `got` where `ref` is finite counts as an element off (|got - ref| > tol is false for a
+    NaN); a non-finite `ref` is an error of its own that names the op's input `xin` (where given): the
+    reference was built from what the plan left there."""
     got, ref = got.float(), ref.float()
+    ref_ok = torch.isfinite(ref)
+    if not ref_ok.all():
+        src = '' if xin is None else (f'; its input: max |x| {xin.float().abs().max().item():.4g}, '
+                                      f'finite {bool(torch.isfinite(xin).all())}')
+        raise AssertionError(f'{what}: {int((~ref_ok).sum())} of {ref.numel()} reference values not finite' + src)
     rms = ref.pow(2).mean().sqrt().item()
     if fp16:   # `ulps` fp16 ulps of the larger of the two (a value just under a power of two may round up)
         tol = torch.maximum(ref.abs(), got.abs()) * 2.0 ** -11 * (2 * ulps) + 1e-4 * rms + 1e-7
     else:
         tol = ref.abs() * 1e-5 + 1e-4 * rms + 1e-12
-    d = (got - ref).abs()
-    bad = d > tol
+    got_ok = torch.isfinite(got)
+    d = torch.where(got_ok, (got - ref).abs(), torch.full_like(ref, float('inf')))
+    bad = ~got_ok | (d > tol)
     nbad = int(bad.sum())
     worst = (d / (ref.abs() + rms + 1e-30)).max().item()
-    assert nbad == 0, (f'{what}: {nbad} of {d.numel()} elements off (max |d| {d.max().item():.3g}, '
-                       f'rms(ref) {rms:.3g}, worst rel {worst:.3g})')
+    assert nbad == 0, (f'{what}: {nbad} of {d.numel()} elements off ({int((~got_ok).sum())} not finite, '
+                       f'max |d| {d.max().item():.3g}, rms(ref) {rms:.3g}, worst rel {worst:.3g})')
     return worst
 
 
@@ -112,7 +127,7 @@ def check_ops(plan, x, B, H, W, raw=None, z=None, skip_fp8=True):
             w, b = _weights(plan, blob, o)
             ref = conv_ref(xin, w, b, s, o['act'])
             got = tv(o['dst'])[..., o['dst_coff']:o['dst_coff'] + o['cout']]
-            out[i] = _ulp_check(got, ref, what, fp16)
+            out[i] = _ulp_check(got, ref, what, fp16, xin=xin)
         elif kind == L.OP_STEM:
             # csrc/stem.hip's arithmetic: with SiLU on both convs, conv A's weights / bias are
             # pre-scaled by -log2(e) (weights rounded to fp16 again), A is stored in fp16 as
@@ -194,6 +209,76 @@ def check_ops(plan, x, B, H, W, raw=None, z=None, skip_fp8=True):
             sc = zr.abs().clamp(min=1.0)
             d = ((z.float() - zr).abs() / sc).max().item()
             assert d <= 1e-5, f'Detect decode: max rel |d| {d:.3g}'
+    return out
+
+
+def decode_ref(logits, stride, anchors):
+    """The Detect decode (yolo.py:52-57) of one level in the logits' own precision: logits [B, ny, nx, na*no]
+    (a 1x1 conv's NHWC output), anchors [na, 2] in pixels -> that level's z rows [B, na*ny*nx, no] in z's row
+    order (anchor, y, x)."""
+    B, ny, nx, c = logits.shape
+    na = anchors.shape[0]
+    no = c // na
+    y = logits.view(B, ny, nx, na, no).permute(0, 3, 1, 2, 4).sigmoid()
+    yv, xv = torch.meshgrid(torch.arange(ny, device=y.device), torch.arange(nx, device=y.device), indexing='ij')
+    grid = torch.stack((xv, yv), 2).view(1, 1, ny, nx, 2).to(y.dtype)
+    ag = anchors.to(y).view(1, na, 1, 1, 2)
+    y = torch.cat(((y[..., 0:2] * 2. - 0.5 + grid) * stride, (y[..., 2:4] * 2) ** 2 * ag, y[..., 4:]), -1)
+    return y.reshape(B, na * ny * nx, no)
+
+
+def check_z_level(zl, logits, stride, anchors, what):
+    """One level's z rows zl [B, na*ny*nx, no] against the float64 decode of float64 reference logits
+    [B, ny, nx, na*no] (anchors [na, 2] in pixels).  Returns the worst |z - z_ref| / bound.
+
+    The bound is the two errors the project already allows, added: the decode's 1e-5 max(|z_ref|, 1), and
+    the logits' dl = 1e-4 max(1, max |logit_ref|) carried through the decode by its largest slope —
+      x, y      (2 s - 0.5 + g) stride   d/dl = 2 s (1 - s) stride        <= 0.5 stride
+      w, h      (2 s)^2 anchor           d/dl = 8 s^2 (1 - s) anchor      <= 32/27 anchor (at s = 2/3)
+      obj, cls  s                        d/dl = s (1 - s)                 <= 0.25
+    (s = sigmoid(logit); the slopes are global maxima, so the bound holds for any perturbation of at most
+    dl, not only to first order).  A z element that is not finite fails."""
+    logits = logits.double()
+    zr = decode_ref(logits, float(stride), anchors.double())
+    assert zl.shape == zr.shape, f'{what}: z rows {tuple(zl.shape)}, reference {tuple(zr.shape)}'
+    na, no = anchors.shape[0], zr.shape[-1]
+    dl = 1e-4 * max(1.0, logits.abs().max().item())
+    slope = torch.full((na, 1, no), 0.25 * dl, dtype=torch.float64, device=zr.device)
+    slope[..., 0:2] = 0.5 * float(stride) * dl
+    slope[..., 2:4] = (32.0 / 27.0) * dl * anchors.double().to(zr.device).view(na, 1, 2)
+    bound = 1e-5 * zr.abs().clamp(min=1.0) + slope.expand(na, zr.shape[1] // na, no).reshape(1, -1, no)
+    finite = torch.isfinite(zl)
+    assert finite.all(), f'{what}: {int((~finite).sum())} of {zl.numel()} z elements not finite'
+    ratio = (zl.double() - zr).abs() / bound
+    worst = ratio.max().item()
+    if worst > 1.0:
+        b, r, c = (int(v) for v in (ratio == ratio.max()).nonzero()[0])
+        raise AssertionError(f'{what}: {int((ratio > 1).sum())} of {ratio.numel()} z elements beyond the bound, worst '
+                             f'{worst:.3g} x at image {b} level row {r} column {c}: {zl[b, r, c].item():.6g} vs '
+                             f'{zr[b, r, c].item():.6g}')
+    return worst
+
+
+def check_detect_z(plan, B, H, W, z):
+    """z [B, N, no] of the last forward against a float64 reference that needs no raw logits: per DETECT op,
+    the 1x1 conv of the op's own input slice (as the plan left it in the workspace) with its packed weights and
+    bias in float64, decoded in float64 (check_z_level).  Returns {level: (op index, worst ratio to the bound)}."""
+    g = plan.graph
+    blob = g.weight_blob().to(plan.device)
+    assert tuple(z.shape) == (B, plan.num_rows(H, W), plan.no), tuple(z.shape)
+    out, row = {}, 0
+    for i, o in sorted(((i, o) for i, o in enumerate(g.ops) if o['kind'] == L.OP_DETECT), key=lambda t: t[1]['level']):
+        lvl = o['level']
+        xin = plan.tensor_view(o['src'], B, H, W)[..., o['src_coff']:o['src_coff'] + o['cin']]
+        what = f'op {i} DETECT level {lvl} ({o["cin"]}->{o["cout"]} @{xin.shape[1]}x{xin.shape[2]})'
+        assert torch.isfinite(xin).all(), f'{what}: its input is not finite'
+        w, b = _weights(plan, blob, o)
+        logits = conv_ref(xin.double(), w.double(), b.double(), 1, L.ACT_NONE)
+        anchors = torch.tensor(g.anchor_grid, dtype=torch.float64, device=z.device).view(g.nl, g.na, 2)[lvl]
+        n = g.na * xin.shape[1] * xin.shape[2]
+        out[lvl] = (i, check_z_level(z[:, row:row + n], logits, g.stride[lvl], anchors, what))
+        row += n
+    assert row == z.shape[1], (row, z.shape)
     return out
 
 

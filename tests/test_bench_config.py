@@ -36,6 +36,23 @@ def _no_miopen():
     torch.backends.cudnn.enabled = prev
 
 
+RB_SENT = 0x7FA5A5A5   # a NaN bit pattern no row record holds
+
+
+def sentinel_buffers(Bq, N, no):
+    """z filled with NaN and row records filled with RB_SENT: torch.empty could hand back the block of an earlier,
+    identical z from the caching allocator, and rows a head never wrote would go unnoticed."""
+    z = torch.full((Bq, N, no), float('nan'), dtype=torch.float32, device=DEV)
+    rb = torch.full((Bq, N, 4), RB_SENT, dtype=torch.int32, device=DEV).view(torch.float32)
+    return z, rb
+
+
+def assert_all_written(z, rb):
+    assert torch.isfinite(z).all(), f'{int((~torch.isfinite(z)).sum())} z elements not written / not finite'
+    left = int((rb.view(torch.int32) == RB_SENT).sum())
+    assert left == 0, f'{left} row-record words left at the sentinel'
+
+
 @pytest.fixture(scope='module')
 def batch():
     return frames(B, H, W, seed=21)
@@ -47,11 +64,11 @@ def test_bench_config_fp16_every_op(batch):
     x = batch.to(DEV).half()
     N = plan.num_rows(H, W)
     # the bench's call: z + row-score records, no raw logits
-    z1 = torch.empty((B, N, plan.no), dtype=torch.float32, device=DEV)
-    rb = torch.empty((B, N, 4), dtype=torch.float32, device=DEV)
+    z1, rb = sentinel_buffers(B, N, plan.no)
     plan.forward_into(x, z1, rowbest=rb)
     z, xs = plan.forward(x)
     torch.cuda.synchronize()
+    assert_all_written(z1, rb)
     assert torch.equal(z, z1), 'raw-logit output changed z'
     out = check_ops(plan, x, B, H, W, raw=xs, z=z)
     print('\nyolov7 640 bs32 fp16: ' + kernel_summary(out))
@@ -146,11 +163,11 @@ def test_w6_config_fp16_every_op():
     plan = m.plan()
     x = xb.to(DEV).half()
     N = plan.num_rows(Hw, Hw)
-    z1 = torch.empty((Bw, N, plan.no), dtype=torch.float32, device=DEV)
-    rb = torch.empty((Bw, N, 4), dtype=torch.float32, device=DEV)
+    z1, rb = sentinel_buffers(Bw, N, plan.no)
     plan.forward_into(x, z1, rowbest=rb)       # bench.py's call
     z, xs = plan.forward(x)
     torch.cuda.synchronize()
+    assert_all_written(z1, rb)
     assert torch.equal(z, z1), 'raw-logit output changed z'
     out = check_ops(plan, x, Bw, Hw, Hw, raw=xs, z=z)
     print('\nyolov7-w6 1280 bs8 fp16: ' + kernel_summary(out))
@@ -187,11 +204,11 @@ def test_tiny_config_fp16_every_op(batch):
     plan = m.plan()
     x = batch.to(DEV).half()
     N = plan.num_rows(H, W)
-    z1 = torch.empty((B, N, plan.no), dtype=torch.float32, device=DEV)
-    rb = torch.empty((B, N, 4), dtype=torch.float32, device=DEV)
+    z1, rb = sentinel_buffers(B, N, plan.no)
     plan.forward_into(x, z1, rowbest=rb)
     z, xs = plan.forward(x)
     torch.cuda.synchronize()
+    assert_all_written(z1, rb)
     assert torch.equal(z, z1), 'raw-logit output changed z'
     out = check_ops(plan, x, B, H, W, raw=xs, z=z)
     print('\nyolov7-tiny 640 bs32 fp16: ' + kernel_summary(out))
@@ -217,11 +234,11 @@ def test_fp8_config_every_op(batch):
     plan = Plan.fp8_from_model(m, DEV)
     x = batch.to(DEV).half()
     N = plan.num_rows(H, W)
-    z = torch.empty((B, N, plan.no), dtype=torch.float32, device=DEV)
-    rb = torch.empty((B, N, 4), dtype=torch.float32, device=DEV)
+    z, rb = sentinel_buffers(B, N, plan.no)
     plan.forward_into(x, z, rowbest=rb)
     z2, xs = plan.forward(x)
     torch.cuda.synchronize()
+    assert_all_written(z, rb)
     assert torch.equal(z, z2)
     out = check_ops(plan, x, B, H, W, raw=xs, z=z2, skip_fp8=True)
     blob = plan.graph.weight_blob()

@@ -19,7 +19,7 @@ import torch
 import family_ref
 from family_nets import fresh
 from helpers import frames
-from opcheck import _ulp_check, _weights, check_ops, conv_ref, kernel_summary, rms_rel
+from opcheck import _ulp_check, _weights, check_detect_z, check_ops, conv_ref, kernel_summary, rms_rel
 from parity import check_z
 from yv7 import _lib as L
 from yv7.runtime import kernel_key
@@ -116,6 +116,25 @@ def check_all(plan, x, B, H, W, z, xs):
     kinds = {o['kind'] for o in plan.graph.ops}
     assert kinds <= {L.OP_INPUT, L.OP_CONV, L.OP_MAXPOOL, L.OP_UPSAMPLE, L.OP_DETECT, L.OP_ADD}, kinds   # all checked
     return out, check_adds(plan, B, H, W)
+
+
+def check_no_raw_call(plan, x, B, H, W, z_raw):
+    """The call without raw logits (the benchmark's): it alone runs the persistent Detect heads (csrc/conv_det.hip;
+    a forward that returns raw logits runs the 64 x 256 ring), so check_ops above never sees them.  z into a
+    NaN-filled buffer with a guard image on either side, against the float64 reference that needs no raw logits
+    (opcheck.check_detect_z), and bit-equal to the raw path's z (the heads promise the ring kernel's arithmetic).
+    Returns a line naming each level's head kernel and its worst ratio to the bound."""
+    N = plan.num_rows(H, W)
+    zbuf = torch.full((B + 2, N, plan.no), float('nan'), dtype=torch.float32, device=x.device)
+    z = zbuf[1:-1]
+    plan.forward_into(x, z)
+    torch.cuda.synchronize()
+    assert torch.isnan(zbuf[0]).all() and torch.isnan(zbuf[-1]).all(), 'z written outside its images'
+    ratios = check_detect_z(plan, B, H, W, z)
+    assert torch.equal(z, z_raw), 'z without raw logits differs from the raw path\'s z'
+    ks = plan.op_kernels(B, H, W)
+    return 'without raw logits: ' + ', '.join(f'K {plan.graph.ops[i]["cin"]} {kernel_key(ks[i][0])} {r:.3g}'
+                                              for _, (i, r) in sorted(ratios.items()))
 
 
 @pytest.mark.parametrize('c', [8, 160])
@@ -265,6 +284,7 @@ def test_mini_e6e_fp16(mini_refs, fuse, monkeypatch):
             worst = max(worst, rms_rel(plan.layer_output(i, B, H, W).cpu(), outs[i]))
     print(f'\nmini-e6e fp16: {kernel_summary(out)}; worst rms-rel err {worst:.3g}')
     assert worst < 0.05
+    print(check_no_raw_call(plan, xg, B, H, W, z))
 
 
 @pytest.mark.parametrize('name,fuse', [('yolov7-e6', 'default'), ('yolov7-d6', 'default'), ('yolov7-e6e', 'default'),
@@ -290,6 +310,11 @@ def test_full_model_fp16_every_op(name, fuse, monkeypatch):
     assert n + nres == (11 if name == 'yolov7-e6e' else 0) and (fuse != 'residual' or nres == 11)
     assert torch.isfinite(z).all()
     print(f'\n{name} fp16 ({fuse}): {kernel_summary(out)}, {n} adds exact, {nres} residual convs')
+    # the head widths of these models (320 / 640 / 960 / 1280, d6: 384 / 768 / 1152 / 1536) in their own graphs:
+    # at this size every level is a single tile, so the one-tile head runs its 5 to 24 K steps
+    line = check_no_raw_call(plan, x, B, H, W, z)
+    print(line)
+    assert line.count('conv_det_1tile_kernel') == 4, line
 
 
 def test_model_api_end_to_end(tmp_path):

@@ -15,7 +15,11 @@ low-resolution 3x3 kernel (270-273: 80 / 64-pixel tiles of 4 images x 4 columns,
 285-288: stride 1; cin 64 / 128, 2-5 ring slots, 2-8-row tiles, with and without the stagger), the register-weight 1x1 kernel (290-295: cin 128 / 256 / 512, with and
 without the stagger; 302 / 303: cin 256 with 128-channel N slices) and
 the alternative Detect heads (92, 97, and 99: the 64 x 256 ring that was the default before the
-persistent head).  A variant a layer's shape
+persistent head; 94: the persistent head with staged weights).  A forward that returns raw logits never runs
+a persistent head (det_pring_supported admits it only without them: 94 then runs the 64 x 256 ring), so the
+Detect variants also run through the call without raw logits, where 94 must launch conv_det_pring_kernel;
+that z is checked against a float64 reference and against the raw path's z (_check_no_raw_call; the default
+heads at their awkward shapes: tests/test_detect_heads.py).  A variant a layer's shape
 does not support runs the register-staged tile kernel instead (conv_f16.hip pick_forced), which the check
 then covers again.
 Reference computation: models/common.py:110-111 (Conv.fuseforward), models/yolo.py:46-57 (Detect).
@@ -24,8 +28,9 @@ import pytest
 import torch
 
 from helpers import fresh_model, frames
-from opcheck import check_ops, kernel_summary
+from opcheck import check_detect_z, check_ops, kernel_summary
 from yv7 import _lib as L
+from yv7.runtime import kernel_key
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -61,9 +66,37 @@ def test_every_conv_variant(name, B, H, W):
         torch.cuda.synchronize()
         out = check_ops(plan, x, B, H, W, raw=xs, z=z)
         lines.append(f'variant {v}: ' + kernel_summary(out))
+        if v in DET_VARIANTS:
+            lines.append(_check_no_raw_call(plan, x, B, H, W, v, dets, z))
         for i in (dets if v in DET_VARIANTS else convs):
             plan.set_op_variant(i, 0)
     print('\n' + '\n'.join(lines))
+
+
+def _check_no_raw_call(plan, x, B, H, W, v, dets, z_raw):
+    """A forced Detect variant through the call without raw logits (the benchmark's): the forward above returns
+    them, and with a raw pointer 94 is not admitted (det_pring_supported) and runs the 64 x 256 ring.  Here 94 must
+    launch conv_det_pring_kernel on every level (both shapes of this test meet det_pring_supported: every level's
+    size, first z row and the rows per image are multiples of 4), and every variant's z must pass the float64
+    reference that needs no raw logits (opcheck.check_detect_z) and equal the raw path's z bit for bit."""
+    ks = plan.op_kernels(B, H, W)
+    for i in dets:
+        head = [kernel_key(k) for k in ks[i]]
+        assert len(head) == 1, (v, i, head)
+        if v == 94:
+            assert head[0] == 'conv_det_pring_kernel<0>', (v, i, head)
+        else:
+            assert not head[0].startswith('conv_det_'), (v, i, head)
+    N = plan.num_rows(H, W)
+    zbuf = torch.full((B + 2, N, plan.no), float('nan'), dtype=torch.float32, device=DEV)
+    z = zbuf[1:-1]
+    plan.forward_into(x, z)
+    torch.cuda.synchronize()
+    assert torch.isnan(zbuf[0]).all() and torch.isnan(zbuf[-1]).all(), f'variant {v}: z written outside its images'
+    ratios = check_detect_z(plan, B, H, W, z)
+    assert torch.equal(z, z_raw), f'variant {v}: z without raw logits differs from the raw path\'s z'
+    heads = ', '.join(f'level {lvl}: {kernel_key(ks[i][0])} {r:.3g}' for lvl, (i, r) in sorted(ratios.items()))
+    return f'variant {v} without raw logits (worst z ratio to the bound): {heads}'
 
 
 # A net with the shapes the fragment kernels mask (ADVICE r4): 3x3 layers with cout % 32 == 16 (cout = 80:
