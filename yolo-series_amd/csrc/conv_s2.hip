@@ -145,12 +145,18 @@ __global__ __launch_bounds__(512, 2) void conv3x3s2_rw_kernel(const ConvParams p
     }
   }
   const uint32_t xoffb = (uint32_t)p.xoff * 2;
+  // tile -> (column group, first row, first image): wave-uniform multiply-highs by the launcher's magic
+  // numbers for ncg and nrg (Div24; T < 2^24), so the decomposition stays on the scalar unit
+  struct Tile { int cg, y0, b0; };
+  auto tile_of = [&](int it) -> Tile {
+    const int t = tw.at(it), tq = div24(t, p.d0);
+    const int ig = div24(tq, p.d1);
+    return Tile{t - tq * ncg, (tq - ig * nrg) * TM, ig * FI};
+  };
   auto tile_base = [&](int it) -> uint32_t {   // byte offset of tile it's first patch pixel (+ xoff)
-    int t = tw.at(it);
-    const int cg = t % ncg;
-    t /= ncg;
-    const int y0 = (t % nrg) * TM, b0 = (t / nrg) * FI;
-    return (uint32_t)(pix_index(b0, S * y0 - 1, S * cg * FC * PG - 1, p.H, p.W) * p.xc * 2) + xoffb;
+    const Tile t = tile_of(it);
+    const uint32_t px = (uint32_t)((t.b0 * (p.H + 2) + S * t.y0) * (p.W + 2) + S * t.cg * FC * PG);
+    return px * (uint32_t)p.xc * 2 + xoffb;   // = pix_index(b0, S y0 - 1, S cg FC PG - 1)
   };
   // the wave's pieces m0 .. m1 - 1 of chunk q (flattened over the block's tiles) into ring slot q % NS;
   // chunks past the last tile read past the tensor (their slots are never read again)
@@ -212,16 +218,28 @@ __global__ __launch_bounds__(512, 2) void conv3x3s2_rw_kernel(const ConvParams p
     }
   };
   const uint32_t lane_ch = (uint32_t)(16 * (g & 1) + 8 * (g >> 1));
+  // the lane's store channels, launch-invariant: byte offset, or past every offset the buffer accepts when
+  // the channel is outside the layer (pixel offsets stay below 2^31, so the sum neither wraps nor lands)
+  constexpr uint32_t CH_OOB = 0x7fffffffu;
+  constexpr int NSC = TN % 2 == 0 ? TN / 2 : TN;
+  uint32_t ch_off[NSC];
+#pragma unroll
+  for (int c = 0; c < NSC; ++c) {
+    const int n = n0 + ng * TN * 16 + (TN % 2 == 0 ? c * 32 + (int)lane_ch : c * 16 + g * 4);
+    ch_off[c] = n < p.cout ? (uint32_t)n * 2 : CH_OOB;
+  }
+  // the lane's output pixel relative to the tile's first (image b0, row y0, column cg FC PG), in bytes; a
+  // tile's rows are one bordered row pitch apart
+  const uint32_t ypitch = (uint32_t)p.yc * 2, yrow = (uint32_t)(p.Wo + 2) * ypitch;
+  const uint32_t y_lane = (uint32_t)(img * (p.Ho + 2) * (p.Wo + 2) + FC * pg + (li & 3)) * ypitch;
   auto epilogue = [&](int it) __attribute__((always_inline)) {
-    int t = tw.at(it);
-    const int cg = t % ncg;
-    t /= ncg;
-    const int y0 = (t % nrg) * TM, b0 = (t / nrg) * FI;
-    const bool live = b0 + img < p.B;
-    const int x = cg * FC * PG + FC * pg + (li & 3);
+    const Tile t = tile_of(it);
+    const uint32_t ybase = (uint32_t)pix_index(t.b0, t.y0, t.cg * FC * PG, p.Ho, p.Wo) * ypitch + (uint32_t)p.yoff * 2;
+    const bool live = img < p.B - t.b0;
+    const uint32_t yo0 = y_lane + ybase;
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
-      const uint32_t yo = live ? (uint32_t)((pix_index(b0 + img, y0 + i, x, p.Ho, p.Wo) * p.yc + p.yoff) * 2) : OOB;
+      const uint32_t yo = live ? yo0 + (uint32_t)i * yrow : OOB;   // (exactly OOB: + CH_OOB must not wrap)
       typedef _Float16 h4 __attribute__((ext_vector_type(4)));
       typedef uint32_t u2 __attribute__((ext_vector_type(2)));
       if constexpr (TN % 2 == 0) {
@@ -237,8 +255,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3s2_rw_kernel(const ConvParams p
           const auto s0 = __builtin_amdgcn_permlane16_swap(a[0], bb[0], false, false);
           const auto s1 = __builtin_amdgcn_permlane16_swap(a[1], bb[1], false, false);
           const u4 v = {s0[0], s1[0], s0[1], s1[1]};
-          const int n = n0 + ng * TN * 16 + mp * 32 + (int)lane_ch;
-          __builtin_amdgcn_raw_buffer_store_b128(v, yr, (live && n < p.cout) ? yo + (uint32_t)n * 2 : 0xffffffffu, 0, 0);
+          __builtin_amdgcn_raw_buffer_store_b128(v, yr, yo + ch_off[mp], 0, 0);
         }
       } else {
 #pragma unroll
@@ -246,9 +263,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3s2_rw_kernel(const ConvParams p
           h4 va;
 #pragma unroll
           for (int e = 0; e < 4; ++e) va[e] = (_Float16)act_t<ACT>(acc[j][i][e]);
-          const int n = n0 + ng * TN * 16 + j * 16 + g * 4;
-          __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2, va), yr,
-                                                (live && n < p.cout) ? yo + (uint32_t)n * 2 : 0xffffffffu, 0, 0);
+          __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2, va), yr, yo + ch_off[j], 0, 0);
         }
       }
     }
@@ -328,8 +343,11 @@ constexpr S2Row s2_rows[] = {
 constexpr int S2_NCFG = sizeof(s2_rows) / sizeof(s2_rows[0]);
 
 template <int ROW, int HOOK = 0>
-hipError_t launch_row(const ConvParams& p, hipStream_t st) {
+hipError_t launch_row(const ConvParams& p0, hipStream_t st) {
   constexpr S2Row r = s2_rows[ROW];
+  ConvParams p = p0;
+  p.d0 = make_div24(p.Wo / (FC * r.pg));   // column groups, row groups per image
+  p.d1 = make_div24(p.Ho / r.tm);
   using G = S2Geo<r.nch, r.tn, r.tm, r.pg, r.ng, r.ns, r.stg, r.s>;
   const int nN = (p.cout + G::BN - 1) / G::BN;
   const long T = (long)((p.B + FI - 1) / FI) * (p.Ho / r.tm) * (p.Wo / (FC * r.pg));

@@ -19,8 +19,14 @@
 //    lane groups, scripts/w1_swizzle_check.py); the swizzle is on the DMA's per-lane source address;
 //  * STG > 0: waves 4-7 run STG intervals behind waves 0-3 (a SIMD hosts w and w + 4), so one group's
 //    tile epilogue issues beside the other group's MFMAs.
-// Pixel m -> bordered NHWC index: m + 2 r + (2 b + 1)(W + 2) + 1, r = m / W, b = r / H (float reciprocal
-// with an exact integer correction; M < 2^24).
+// Pixel m -> bordered NHWC index: m + 2 r + (2 b + 1)(W + 2) + 1, r = m / W, b = r / H.  Only the tile's
+// first pixel m0 is decomposed, once per tile and wave-uniform (Div24 multiply-highs, scalar unit); a lane's
+// pixel m0 + off then lies floor((c0 + off) / W) rows on (c0 = m0's column) and past the image's last row
+// iff off >= (H - h0) W - c0, so its index is base(m0) + off + 2 [off >= W - c0] + 2 [off >= 2 W - c0] +
+// 2 (W + 2) [next image]: compares of the lane's launch-invariant offset against per-tile scalars, no
+// division and no multiply per lane.  That needs a tile to wrap at most NWR = 2 rows (TPX - 2 < 2 W) and
+// one image (H >= 2); narrower tensors keep the per-lane decomposition bpix() (float reciprocal with an
+// exact integer correction; M < 2^24).
 #include "yv7_kernels.h"
 
 namespace yv7 {
@@ -28,6 +34,7 @@ namespace yv7 {
 namespace {
 
 constexpr int DC = 64;          // channels per DMA chunk (one 128-byte line per pixel; two MFMA K steps)
+constexpr int NWR = 2;          // row wraps inside a tile the stepped index covers
 
 // bordered pixel index of output pixel m (H, W: the tensor's interior size; rW = 1 / W, rH = 1 / H)
 __device__ __forceinline__ uint32_t bpix(int m, int H, int W, float rW, float rH) {
@@ -38,6 +45,29 @@ __device__ __forceinline__ uint32_t bpix(int m, int H, int W, float rW, float rH
   if ((b + 1) * H <= r) ++b;
   if (b * H > r) --b;
   return (uint32_t)(m + 2 * r + (2 * b + 1) * (W + 2) + 1);
+}
+
+// Wave-uniform decomposition of a tile's first pixel m0: idx = its bordered index; offsets off >= t1 + w W
+// (w = 0 .. NWR - 1) are w + 1 rows on, offsets >= tb in the next image, offsets >= rem past the tensor.
+struct TileBase {
+  uint32_t idx;
+  int t1, tb, rem;
+};
+__device__ __forceinline__ TileBase tile_base(int m0, const ConvParams& p) {
+  const int R0 = div24(m0, p.d0), c0 = m0 - R0 * p.Wo;
+  const int b0 = div24(R0, p.d1), h0 = R0 - b0 * p.Ho;
+  return TileBase{(uint32_t)(m0 + 2 * R0 + (2 * b0 + 1) * (p.Wo + 2) + 1), p.Wo - c0, (p.Ho - h0) * p.Wo - c0,
+                  p.M - m0};
+}
+// Byte offset of the lane's pixel at tile offset lo + ok (lo: the lane's part, ok: wave-uniform) given the
+// offset `s` of the same pixel were it on the tile's first row: + row2 per wrapped row (2 border pixels),
+// + img2 into the next image (2 border rows); OOB past the tensor.
+__device__ __forceinline__ uint32_t step_pix(uint32_t s, int lo, int ok, const TileBase& tb, int W, uint32_t row2,
+                                             uint32_t img2) {
+#pragma unroll
+  for (int w = 0; w < NWR; ++w) s += lo >= tb.t1 + w * W - ok ? row2 : 0u;
+  s += lo >= tb.tb - ok ? img2 : 0u;
+  return lo < tb.rem - ok ? s : OOB;
 }
 
 template <int NCH, int TN, int TPF, int PG, int NG, int NS, int STG, int IC>
@@ -115,9 +145,39 @@ __global__ __launch_bounds__(512, 2) void conv1x1_rw_kernel(const ConvParams p, 
   // chunk k / PPC, pixels 8 (k % PPC) .. + 7; lane -> pixel 8 (k % PPC) + lane / 8, LDS position lane % 8
   // = source part (lane % 8) ^ ((px >> 1) & 7) of the chunk's 128-byte line
   const uint32_t xoffb = (uint32_t)p.xoff * 2, pitch = (uint32_t)p.xc * 2;
+  // stepped index (header): a tile wraps at most NWR rows and one image; launch-invariant
+  // (TIGHT: two kinds of slice keep the per-lane decomposition and the per-store channel test.  Where the weights
+  // and accumulators fill the register file, the lane's parts held across the tile loop would cost VGPRs those
+  // configurations do not have (they spill); and the cin-512 slices, NCH 16, measured 3-5 % slower per launch
+  // with the stepped index in the yolov7 bs-32 forward, profiles/addr_trim/README.md)
+  constexpr bool TIGHT = TN * (NCH + TPF) * 4 >= 192 || NCH == 16;
+  const bool stepped = !TIGHT && G::TPX - 2 < NWR * p.Wo && p.Ho >= NWR;
   uint32_t src[G::PW];   // per-lane source offsets of the tile's pieces (chunk within the interval folded in)
+  // a piece's pixel offset is 8 (k % PPC) + lane / 8 with k % 2 = wave % 2 (PPC is even), so the swizzle term
+  // (px >> 1) & 7 = 4 (wave & 1) | lane / 16 is the lane's for the whole launch
+  const int lo8 = lane >> 3;
+  const uint32_t dma_lane = (uint32_t)lo8 * pitch + (uint32_t)(((lane & 7) ^ (lane >> 4) ^ (4 * (wave & 1))) * 16);
   auto set_tile = [&](int it) __attribute__((always_inline)) {
     const int m0 = it < ntl ? tw.at(it) * G::TPX : p.M;
+    if (stepped) {
+      const TileBase tb = tile_base(m0, p);
+      const uint32_t base = tb.idx * pitch + xoffb;
+      // the wave's pieces k = wave + 8 mm cover only NPX different pixel groups k % PPC (PPC / 8 of them, or
+      // one when PPC = 4), each in several chunks k / PPC: one stepped offset per group, + the chunk's
+      constexpr int NPX = G::PPC >= 8 ? G::PPC / 8 : 1;
+      static_assert(G::PPC % 8 == 0 || G::PPC == 4, "pixel groups of a wave's pieces");
+      uint32_t pa[NPX];
+#pragma unroll
+      for (int j = 0; j < NPX; ++j) {
+        const int ok = ((wave + 8 * j) % G::PPC) * 8;
+        pa[j] = step_pix(dma_lane + (base + (uint32_t)ok * pitch), lo8, ok, tb, p.Wo, 2 * pitch,
+                         2 * (uint32_t)(p.Wo + 2) * pitch);
+      }
+#pragma unroll
+      for (int mm = 0; mm < G::PW; ++mm)   // (OOB + a chunk offset stays past every tensor)
+        src[mm] = pa[mm % NPX] + (uint32_t)(((wave + 8 * mm) / G::PPC) * DC * 2);
+      return;
+    }
 #pragma unroll
     for (int mm = 0; mm < G::PW; ++mm) {
       const int k = wave + 8 * mm;
@@ -170,14 +230,49 @@ __global__ __launch_bounds__(512, 2) void conv1x1_rw_kernel(const ConvParams p, 
                                                                __builtin_bit_cast(h8, xa[f]), acc[j][f], 0, 0, 0);
       }
   };
-  const uint32_t lane_ch = (uint32_t)(16 * (g & 1) + 8 * (g >> 1));
+  // the lane's store channels, launch-invariant: byte offset, or past every offset the buffer accepts when
+  // the channel is outside the layer (pixel offsets stay below 2^31, so the sum neither wraps nor lands)
+  constexpr uint32_t CH_OOB = 0x7fffffffu;
+  constexpr int NSC = TN % 2 == 0 ? TN / 2 : TN;
+  const uint32_t ypitch = (uint32_t)p.yc * 2;
+  const uint32_t y_lane = (uint32_t)li * ypitch;
+  uint32_t ch_off[NSC];
+#pragma unroll
+  for (int c = 0; c < NSC; ++c) {
+    const int n = n0 + ng * TN * 16 + (TN % 2 == 0 ? c * 32 + 16 * (g & 1) + 8 * (g >> 1) : c * 16 + g * 4);
+    ch_off[c] = n < p.cout ? (uint32_t)n * 2 : CH_OOB;
+  }
+  // a store's offset: TIGHT keeps the test per store
+  auto st_off = [&](uint32_t yo, bool live, int c) __attribute__((always_inline)) {
+    if constexpr (TIGHT) {
+      const int n = n0 + ng * TN * 16 + (TN % 2 == 0 ? c * 32 + 16 * (g & 1) + 8 * (g >> 1) : c * 16 + g * 4);
+      return (live && n < p.cout) ? yo + (uint32_t)n * 2 : 0xffffffffu;
+    } else {
+      return yo + ch_off[c];
+    }
+  };
   auto epilogue = [&](int it) __attribute__((always_inline)) {
-    const int m0 = tw.at(it) * G::TPX + pg * TPF * 16 + li;
+    const int mt = tw.at(it) * G::TPX;
+    const int m0 = mt + pg * TPF * 16 + li;
+    TileBase tb{};
+    uint32_t ybase = 0;
+    if (stepped) {
+      tb = tile_base(mt, p);
+      ybase = tb.idx * ypitch + (uint32_t)p.yoff * 2;
+    }
 #pragma unroll
     for (int f = 0; f < TPF; ++f) {
-      const int m = m0 + f * 16;
-      const bool live = m < p.M;
-      const uint32_t yo = live ? (uint32_t)((bpix(m, p.Ho, p.Wo, rW, rH) * p.yc + p.yoff) * 2) : OOB;
+      uint32_t yo;
+      bool live = true;   // (only TIGHT's stores look at it)
+      if (stepped) {
+        const int ok = pg * TPF * 16 + f * 16;
+        yo = step_pix(y_lane + (ybase + (uint32_t)ok * ypitch), li, ok, tb, p.Wo, 2 * ypitch,
+                      2 * (uint32_t)(p.Wo + 2) * ypitch);
+      } else {
+        const int m = m0 + f * 16;
+        live = m < p.M;
+        yo = live ? (uint32_t)((bpix(m, p.Ho, p.Wo, rW, rH) * p.yc + p.yoff) * 2) : OOB;
+      }
       typedef _Float16 h4 __attribute__((ext_vector_type(4)));
       typedef uint32_t u2 __attribute__((ext_vector_type(2)));
       if constexpr (TN % 2 == 0) {
@@ -193,8 +288,7 @@ __global__ __launch_bounds__(512, 2) void conv1x1_rw_kernel(const ConvParams p, 
           const auto s0 = __builtin_amdgcn_permlane16_swap(a[0], bb[0], false, false);
           const auto s1 = __builtin_amdgcn_permlane16_swap(a[1], bb[1], false, false);
           const u4 vv = {s0[0], s1[0], s0[1], s1[1]};
-          const int n = n0 + ng * TN * 16 + mp * 32 + (int)lane_ch;
-          __builtin_amdgcn_raw_buffer_store_b128(vv, yr, (live && n < p.cout) ? yo + (uint32_t)n * 2 : 0xffffffffu, 0, 0);
+          __builtin_amdgcn_raw_buffer_store_b128(vv, yr, st_off(yo, live, mp), 0, 0);
         }
       } else {
 #pragma unroll
@@ -202,9 +296,7 @@ __global__ __launch_bounds__(512, 2) void conv1x1_rw_kernel(const ConvParams p, 
           h4 va;
 #pragma unroll
           for (int e = 0; e < 4; ++e) va[e] = (_Float16)act_t<ACT>(acc[j][f][e]);
-          const int n = n0 + ng * TN * 16 + j * 16 + g * 4;
-          __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2, va), yr,
-                                                (live && n < p.cout) ? yo + (uint32_t)n * 2 : 0xffffffffu, 0, 0);
+          __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2, va), yr, st_off(yo, live, j), 0, 0);
         }
       }
     }
@@ -288,8 +380,11 @@ constexpr W1Row w1_rows[] = {
 constexpr int W1_NCFG = sizeof(w1_rows) / sizeof(w1_rows[0]);
 
 template <int ROW, int HOOK = 0>
-hipError_t launch_row(const ConvParams& p, hipStream_t st) {
+hipError_t launch_row(const ConvParams& p0, hipStream_t st) {
   constexpr W1Row r = w1_rows[ROW];
+  ConvParams p = p0;
+  p.d0 = make_div24(p.Wo);
+  p.d1 = make_div24(p.Ho);
   using G = W1Geo<r.nch, r.tn, r.tpf, r.pg, r.ng, r.ns, r.stg, r.ic>;
   const int nN = (p.cout + G::BN - 1) / G::BN;
   const long T = ((long)p.M + G::TPX - 1) / G::TPX;

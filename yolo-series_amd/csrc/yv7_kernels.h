@@ -162,6 +162,20 @@ __device__ __forceinline__ void vmwait() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
+// n / d for 0 <= n < 2^24 and 1 <= d <= 2^24 as one multiply-high: mul = ceil(2^(24 + sh) / d) with
+// sh = ceil(log2 d), so mul <= 2^25 and n * (mul * d - 2^(24 + sh)) < 2^24 * d <= 2^(24 + sh): the quotient is
+// exact (d = 1: mul = 2^24, sh = 0).  On a wave-uniform n this is s_lshl + s_mul_hi_u32 + s_lshr — a
+// persistent kernel's once-per-tile decomposition of its first pixel (tests/test_addr_trim_cpu.py restates it).
+struct Div24 {
+  uint32_t mul, sh;
+};
+inline Div24 make_div24(int d) {
+  uint32_t s = 0;
+  while ((1u << s) < (uint32_t)d) ++s;
+  return Div24{(uint32_t)(((1ull << (24 + s)) + (uint64_t)d - 1) / (uint64_t)d), s};
+}
+__device__ __forceinline__ int div24(int n, Div24 d) { return (int)(__umulhi((uint32_t)n << 8, d.mul) >> d.sh); }
+
 // Kernel parameters of one conv launch (also the fused Detect head).
 struct ConvParams {
   const void* x;      // bordered NHWC input tensor (allocation start)
@@ -197,6 +211,9 @@ struct ConvParams {
   const void* res;
   uint32_t rbytes;
   int rc, roff;
+  // the two divisors of a persistent kernel's tile decomposition, filled in by the launchers of the kernels
+  // that use them (conv_w1.hip: Wo, Ho; conv_s2.hip: column groups, row groups per image)
+  Div24 d0, d1;
 };
 
 // The max-pooled second consumer of a register-streamed 1x1 conv's input (conv_rs.hip): the MP block's
