@@ -1,11 +1,13 @@
 """Shared fixtures: product model + seeded synthetic weights, and the oracle fed the same weights."""
 from __future__ import annotations
 
+import ctypes
 import functools
 
 import torch
 
 from models.yolo import Model
+from yv7 import _lib as L
 from yv7.synthetic import synthetic_frames, synthetic_state_dict
 
 
@@ -38,3 +40,12 @@ def fresh_model(name: str, seed: int = 0, fuse=True):
 
 def frames(B, H, W, seed=1):
     return synthetic_frames(B, H, W, seed=seed)
+
+
+def bordered(plan, t, B, H, W):
+    """The whole NHWC tensor t of the last forward, zero frame included."""
+    off, dims = ctypes.c_int64(), (ctypes.c_int64 * 4)()
+    L.check(L.lib().yv7_tensor_info(plan._h, t, B, H, W, ctypes.byref(off), dims), 'yv7_tensor_info')
+    dt = torch.float16 if plan.dtype == L.DT_F16 else torch.float32
+    n = dims[0] * dims[1] * dims[2] * dims[3]
+    return plan.workspace(B, H, W)[off.value:off.value + n * dt.itemsize].view(dt).view(*dims)

@@ -16,6 +16,8 @@ Convolutions run as sums of per-tap fp32 matmuls on the device (no MIOpen: nothi
 run time).  Tolerances: an fp16 output within one fp16 ulp of the fp32 reference (+1e-4 of the op's
 rms for the accumulation order; two ulps for the fused stem, whose intermediate is fp16); fp32 outputs within 1e-5 |ref| + 1e-4 rms; max / upsample / copy exact.
 An output that is not finite is an element off; a reference that is not finite is an error naming the op's input.
+check_ops reads the image interiors only (it pads its references itself), so it does not see a kernel that writes the
+zero frame around an image: tests/test_gemm_edges.py and tests/test_family_gpu.py check the frames (helpers.bordered).
 
 check_ops checks DETECT through the raw logits, and a forward that returns them never runs the persistent heads
 (csrc/conv_det.hip).  check_detect_z checks z alone: per level a float64 conv + decode of the op's own input

@@ -11,14 +11,13 @@ from float64, on every element).  fp16 plan: per layer and z, the rms-relative 0
 tests/test_gpu_forward.py::test_forward_fp16_layerwise_scale.
 """
 import copy
-import ctypes
 
 import pytest
 import torch
 
 import family_ref
 from family_nets import fresh
-from helpers import frames
+from helpers import bordered, frames
 from opcheck import _ulp_check, _weights, check_detect_z, check_ops, conv_ref, kernel_summary, rms_rel
 from parity import check_z
 from yv7 import _lib as L
@@ -34,15 +33,6 @@ def _no_miopen():
     torch.backends.cudnn.enabled = False
     yield
     torch.backends.cudnn.enabled = prev
-
-
-def bordered(plan, t, B, H, W):
-    """The whole NHWC tensor t of the last forward, zero frame included."""
-    off, dims = ctypes.c_int64(), (ctypes.c_int64 * 4)()
-    L.check(L.lib().yv7_tensor_info(plan._h, t, B, H, W, ctypes.byref(off), dims), 'yv7_tensor_info')
-    dt = torch.float16 if plan.dtype == L.DT_F16 else torch.float32
-    n = dims[0] * dims[1] * dims[2] * dims[3]
-    return plan.workspace(B, H, W)[off.value:off.value + n * dt.itemsize].view(dt).view(*dims)
 
 
 def check_adds(plan, B, H, W):

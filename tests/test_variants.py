@@ -21,7 +21,9 @@ Detect variants also run through the call without raw logits, where 94 must laun
 that z is checked against a float64 reference and against the raw path's z (_check_no_raw_call; the default
 heads at their awkward shapes: tests/test_detect_heads.py).  A variant a layer's shape
 does not support runs the register-staged tile kernel instead (conv_f16.hip pick_forced), which the check
-then covers again.
+then covers again; test_every_conv_variant prints, per variant, the ops on which another kernel than that fallback
+launched, and test_variants_that_launch_nowhere pins the variants that only ever fall back on both networks
+(tests/test_gemm_edges.py and tests/test_addr_trim.py hold every variant to its own kernel on nets built for it).
 Reference computation: models/common.py:110-111 (Conv.fuseforward), models/yolo.py:46-57 (Detect).
 """
 import pytest
@@ -41,6 +43,12 @@ CONV_VARIANTS = [1, 2, 4, 5, 6, 7, 8, 10, 11, 15, 17,
                  277, 278, 279, 280, 281, 282, 283, 284, 285, 286, 287, 288, 290, 291, 292, 293,
                  294, 295, 302, 303]
 DET_VARIANTS = [92, 94, 97, 99]
+NETWORKS = [('yolov7', 2, 256, 256), ('yolov7-tiny', 2, 192, 256)]
+# The forced variants that launch nothing but the fallback on every conv op of both networks at these frames: today's
+# silent fallbacks, pinned so that a dispatch change which adds one shows up.  (Six configurations of conv_lr.hip whose
+# tile heights divide no map of these frames; tests/test_addr_trim.py launches them.)
+LAUNCH_NOWHERE = [270, 271, 275, 276, 277, 279]
+LAUNCHED = {}   # network -> {variant: [ops on which a kernel other than the fallback launched]}
 
 
 @pytest.fixture(scope='module', autouse=True)
@@ -51,7 +59,24 @@ def _no_miopen():
     torch.backends.cudnn.enabled = prev
 
 
-@pytest.mark.parametrize('name,B,H,W', [('yolov7', 2, 256, 256), ('yolov7-tiny', 2, 192, 256)])
+def fallback_key(o):
+    """The kernel a forced variant runs on conv op o where its form does not apply: the register-staged tile kernel by
+    output width (csrc/conv_f16.hip pick_tile, the rows of conv_f16_launch.h tile_rows).  (The kernels of forced variant
+    1 itself are another family: without a residual, csrc/conv.hip launch_conv sends it to that file's generic kernel.)"""
+    bn, wm = (32, 4) if o['cout'] <= 32 else (64, 2) if o['cout'] <= 64 else (128, 2)
+    one = o.get('k', 1) == 1 and o.get('s', 1) == 1 and o.get('pad', 0) == 0
+    return f'conv_f16_kernel<128, {bn}, {wm}, {"true" if one else "false"}, false, 1, false>'
+
+
+def launched_elsewhere(plan, B, H, W):
+    """The conv ops (MP-folded ones aside: their kernel is the pooled tile whatever the variant) on which the variants
+    now set launch a kernel other than the fallback (a dry run)."""
+    ks = plan.op_kernels(B, H, W)
+    return [i for i, o in enumerate(plan.graph.ops) if o['kind'] == L.OP_CONV and not o.get('pool') and
+            any(kernel_key(k) != fallback_key(o) for k in ks[i])]
+
+
+@pytest.mark.parametrize('name,B,H,W', NETWORKS)
 def test_every_conv_variant(name, B, H, W):
     m = fresh_model(name).to(DEV).half()
     plan = m.plan()
@@ -59,9 +84,13 @@ def test_every_conv_variant(name, B, H, W):
     convs = [i for i, o in enumerate(plan.graph.ops) if o['kind'] == L.OP_CONV]
     dets = [i for i, o in enumerate(plan.graph.ops) if o['kind'] == L.OP_DETECT]
     lines = []
+    LAUNCHED[name] = {}
     for v in CONV_VARIANTS + DET_VARIANTS:
         for i in (dets if v in DET_VARIANTS else convs):
             plan.set_op_variant(i, v)
+        if v in CONV_VARIANTS:
+            LAUNCHED[name][v] = launched_elsewhere(plan, B, H, W)
+            lines.append(f'variant {v}: a kernel other than the fallback on ops {LAUNCHED[name][v]}')
         z, xs = plan.forward(x)
         torch.cuda.synchronize()
         out = check_ops(plan, x, B, H, W, raw=xs, z=z)
@@ -71,6 +100,23 @@ def test_every_conv_variant(name, B, H, W):
         for i in (dets if v in DET_VARIANTS else convs):
             plan.set_op_variant(i, 0)
     print('\n' + '\n'.join(lines))
+
+
+def test_variants_that_launch_nowhere():
+    """Over both networks of test_every_conv_variant (a network that test has not run in this session is dry-run here),
+    the variants whose own kernel launches on no conv op are exactly LAUNCH_NOWHERE."""
+    for name, B, H, W in NETWORKS:
+        if name in LAUNCHED:
+            continue
+        plan = fresh_model(name).to(DEV).half().plan()
+        convs = [i for i, o in enumerate(plan.graph.ops) if o['kind'] == L.OP_CONV]
+        LAUNCHED[name] = {}
+        for v in CONV_VARIANTS:
+            for i in convs:
+                plan.set_op_variant(i, v)
+            LAUNCHED[name][v] = launched_elsewhere(plan, B, H, W)
+    nowhere = [v for v in CONV_VARIANTS if not any(LAUNCHED[name][v] for name, *_ in NETWORKS)]
+    assert nowhere == LAUNCH_NOWHERE, nowhere
 
 
 def _check_no_raw_call(plan, x, B, H, W, v, dets, z_raw):
