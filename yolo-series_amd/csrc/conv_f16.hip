@@ -2,7 +2,7 @@
 // KRSC weights: the dispatch.  This file is host code; it decides which kernel a layer runs (pick) and
 // launches it (launch_pick).  The kernels live one family per file: conv_f16_ring.hip (register-staged
 // tile kernel, 8-wave LDS-DMA ring with split-K), conv_f16_pring.hip (persistent ring and its
-// weight-stationary forms), conv_f16_p8.hip (8-phase rings), conv_det.hip (Detect heads), and the 3x3 /
+// weight-stationary forms), conv_f16_p8.hip (8-phase rings), conv_det.hip / conv_det_nc.hip (Detect heads), and the 3x3 /
 // register-weight kernels of conv_lr / conv_s2 / conv_w1 / conv_hring / conv_ws / conv_halo.hip.
 //
 // Replaces ATen conv2d + BN-folded bias + SiLU/LeakyReLU (Conv.fuseforward models/common.py:110-111,
@@ -53,7 +53,7 @@ int env_lr() {
 
 // What the dispatch decided for one layer: the kernel family, its configuration (a row of the family's
 // table in conv_f16_launch.h, or the cfg of the family's own launcher) and K splits.
-enum Family { F_INVALID, F_TILE, F_RING, F_PRING, F_P8, F_DET, F_LR, F_S2, F_W1, F_HRING, F_WS64, F_HALO };
+enum Family { F_INVALID, F_TILE, F_RING, F_PRING, F_P8, F_DET, F_DETNC, F_LR, F_S2, F_W1, F_HRING, F_WS64, F_HALO };
 struct Pick {
   Family fam;
   int cfg = 0;
@@ -192,8 +192,25 @@ Pick pick_pool(const ConvParams& p, bool det) {
 
 Pick pick_det(const ConvParams& p, int variant) {
   // Detect head: the persistent head (conv_det_pring_kernel) where it applies; 98 = its
-  // microbenchmark hook (no staging), 99 = the 64 x 256 ring below (the round-2 default)
+  // microbenchmark hook (no staging), 99 = the 64 x 256 ring below (the round-2 default).
+  // DETECT variants: 89 = the class-count-generic head (conv_det_nc_kernel), 92 = the 64 x 256 tile kernel,
+  // 94 = the persistent head with staged weights, 97 = the 128 x 256 ring, 99 = the 64 x 256 ring (the ABI
+  // accepts these five); 91 / 93 / 95 / 96 / 98 = microbenchmark hooks of the (3, 85) heads.
   static const int det_pring = env_int("YV7_DET_PRING", 1);
+  // Every head but the standard (na, no) = (3, 85) — with or without raw logits — runs the class-count-
+  // generic head (conv_det_nc.hip: per-anchor tiles of the head's own width); variant 89 forces it on any
+  // head, the standard one included.  The 256-wide forms below decode ONE N tile as channels 0 .. 255, so a
+  // head with more channels (na * no > 256) is refused there, forced or not.
+  // Measured against the 64 x 256 ring (bs 32, 256 @80^2 / 512 @40^2 / 1024 @20^2, us, ring -> this head,
+  // profiles/det_nc/): nc 1 94.6 / 36.0 / 26.8 -> 53.3 / 22.6 / 13.3, nc 20 122 / 45.6 / 31.6 -> 68.3 / 27.7 /
+  // 15.3, nc 40 139 / 50.4 / 34.1 -> 103 / 37.1 / 19.2, nc 59 154 / 54.1 / 35.0 -> 126 / 45.4 / 22.5, nc 70
+  // 158-159 / 55.0 / 36.3 -> 155-156 / 51.9 / 24.1; nc 79 (252 channels: the ring's tile is full, this head
+  // computes 3 x 96) 159-161 / 54.3 / 36.0 -> 164-167 / 56.4-57.4 / 25.0-26.7.  So the ring keeps the heads
+  // that fill more than 15/16 of its tile (240 < na * no < 256) on levels of more than one 64-pixel tile per CU.
+  if ((variant == 89 || (variant == 0 && !(p.na == 3 && p.no == 85))) && det_nc_supported(p)) {
+    const bool ring_wins = p.cout > 240 && p.cout < 256 && (p.M + 63) / 64 > device_cus();
+    if (variant == 89 || !ring_wins) return {F_DETNC};
+  }
   if (((variant == 0 && det_pring) || variant == 94 || variant == 98 || variant == 96 || variant == 95 ||
        variant == 93 || variant == 91) && det_pring_supported(p))
     return {F_DET};
@@ -201,6 +218,7 @@ Pick pick_det(const ConvParams& p, int variant) {
   // (scripts/detbench.hip, bs 32, row scores on: 64 x 256 ring, 2 blocks per CU so one block's
   // epilogue runs beside the other's main loop: 124 / 42 / 25 us at 80 / 40 / 20; 128 x 256 ring
   // 127 / 42 / 29; register-staged 64 x 256 tile 141 / 47 / 30)
+  if (p.cout > 256) return {F_INVALID};
   if (variant == 92) return {F_TILE, T64x256det};
   if (variant == 97) return {F_RING, R128x256det};
   return {F_RING, R64x256det};
@@ -505,6 +523,7 @@ hipError_t launch_pick(const ConvParams& p, const Pick& k, hipStream_t st) {
     case F_PRING: return launch_pring(p, k.cfg, st);
     case F_P8: return launch_p8(p, k.cfg, st);
     case F_DET: return launch_det_pring(p, st);
+    case F_DETNC: return launch_det_nc(p, st);
     case F_LR: return launch_conv_lr(p, k.cfg, st);
     case F_S2: return launch_conv_s2(p, k.cfg, st);
     case F_W1: return launch_conv_w1(p, k.cfg, st);

@@ -1,5 +1,5 @@
 // Private interface between the fp16 dispatch (conv_f16.hip) and the kernel families it launches
-// (conv_f16_ring.hip, conv_f16_pring.hip, conv_f16_p8.hip, conv_det.hip).  Each family exports one
+// (conv_f16_ring.hip, conv_f16_pring.hip, conv_f16_p8.hip, conv_det.hip, conv_det_nc.hip).  Each family exports one
 // non-template launch function per kernel, selected by a row of the family's table below: the tables
 // list every instantiation the library holds.  An unknown row is hipErrorInvalidValue.
 #pragma once
@@ -70,6 +70,13 @@ hipError_t launch_p8(const ConvParams& p, int cfg, hipStream_t st);
 // conv_det_rw_kernel); launch_det_pring picks among them and reads p.variant for their forced forms / hooks
 bool det_pring_supported(const ConvParams& p);
 hipError_t launch_det_pring(const ConvParams& p, hipStream_t st);
+
+// conv_det_nc.hip: the class-count-generic Detect head (conv_det_nc_kernel<NW>): any na <= 4 and any no up
+// to its widest compile-time tile, with or without raw logits.  det_nc_width: the tile width a head of `no`
+// values per anchor runs (0: none)
+int det_nc_width(int no);
+bool det_nc_supported(const ConvParams& p);
+hipError_t launch_det_nc(const ConvParams& p, hipStream_t st);
 
 // A kernel configuration of the fp16 CONV dispatch the ABI may force (yv7_set_op_variant), as opposed
 // to a microbenchmark hook or no variant at all: read from the dispatch's forced-variant table.

@@ -517,6 +517,7 @@ __global__ __launch_bounds__(64 * WM * WN, (STAGES * (BM + BN) * 128 <= 80 * 102
 template <int BM, int BN, int WM, bool ONE, bool DET, int PF, bool POOL, bool RES>
 hipError_t launch_t(const ConvParams& p, hipStream_t st) {
   const int nM = (p.M + BM - 1) / BM, nN = (p.cout + BN - 1) / BN;
+  if (DET && p.cout > BN) return hipErrorInvalidValue;   // det_epilogue decodes one N tile: channels 0 .. BN - 1
   if constexpr (RES) {
     static_assert(!DET && !POOL && PF == 1, "the residual rows are plain tiles");
     if (!p.res) return hipErrorInvalidValue;
@@ -531,6 +532,7 @@ hipError_t launch_t(const ConvParams& p, hipStream_t st) {
 template <int BM, int BN, int WM, int WN, int STAGES, bool ONE, bool DET, bool RES>
 hipError_t launch_r(const ConvParams& p0, int S, hipStream_t st) {
   ConvParams p = p0;
+  if (DET && p.cout > BN) return hipErrorInvalidValue;   // det_epilogue decodes one N tile: channels 0 .. BN - 1
   const long tiles = (long)((p.M + BM - 1) / BM) * ((p.cout + BN - 1) / BN);
   unsigned nblk = (unsigned)tiles;
   if (S >= 1) {

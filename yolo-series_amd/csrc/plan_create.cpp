@@ -159,7 +159,7 @@ bool variant_allowed(const yv7_op_desc& o, int v) {
   if (v == 0) return true;
   const int kind = o.kind;
   if (is_f8(o)) return v == 81 || v == 82;   // fp8 1x1: staged quantize pass / fused quantization
-  if (kind == YV7_OP_DETECT) return v == 92 || v == 94 || v == 97 || v == 99;
+  if (kind == YV7_OP_DETECT) return v == 89 || v == 92 || v == 94 || v == 97 || v == 99;   // 89: conv_det_nc.hip
   if (v == 305) return o.k == 3 && o.s == 1;   // the chained launch of the 3x3 stack starting here (find_chain)
   return yv7::conv_f16_variant_is_config(v);
 }
@@ -270,6 +270,9 @@ int yv7_set_op_variant(yv7_plan* p, int op, int variant) {
     return fail(YV7_E_ARG, "yv7_set_op_variant: op " + std::to_string(op) + " is not a CONV / DETECT op");
   if (!variant_allowed(o, variant))
     return fail(YV7_E_ARG, "yv7_set_op_variant: variant " + std::to_string(variant) + " is not a kernel configuration");
+  if (o.kind == YV7_OP_DETECT && o.cout > 256 && (variant == 92 || variant == 97 || variant == 99))
+    return fail(YV7_E_ARG, "yv7_set_op_variant: variant " + std::to_string(variant) + " is a 256-channel Detect form; op " +
+                               std::to_string(op) + " has na * no = " + std::to_string(o.cout) + " > 256");
   if (o.kind == YV7_OP_CONV && o.src2 >= 0 && variant != 0 && !yv7::conv_f16_variant_has_residual(variant))
     return fail(YV7_E_ARG, "yv7_set_op_variant: op " + std::to_string(op) + " carries a residual; variant " +
                                std::to_string(variant) + " is of a kernel family without the residual epilogue");
