@@ -25,6 +25,8 @@
  *                     sizes on one canvas                       letterbox loop, np.stack, transpose, / 255)
  *   yv7_scale_boxes   scale_coords() + clip_coords(),           utils/general.py:340-361, detect.py:183,
  *                     .round(), the Detections views            models/common.py:940-948
+ *   yv7_match         the per-image, per-class matching of      test.py:123,131,179-213
+ *                     predictions to labels for mAP
  */
 #ifndef YV7_H
 #define YV7_H
@@ -257,6 +259,25 @@ typedef struct {
 
 int yv7_scale_boxes(float* det, const int32_t* count, int B, int max_det, const yv7_scale_desc* images,
                     int round_boxes, float* xywh, float* xyxyn, float* xywhn, void* stream);
+
+/* Predictions matched to labels for mAP (replaces test.py:179-213, the per-image, per-class loop with .item()
+ * inside, together with the labels' way to native pixels, test.py:123,131,186-187), for the whole batch in one
+ * launch per 64 images and without a host sync.
+ * det, count: yv7_nms's output AFTER yv7_scale_boxes, i.e. boxes in each image's own pixels.  targets: device
+ * [L,6] rows (image, class, x, y, w, h) normalised to the canvas_h x canvas_w canvas, sorted by image;
+ * label_off: device [B+1] with image b's labels in rows label_off[b] .. label_off[b+1] (0 first, L last).
+ * images: host array, passed on by value, of the descriptors of scale_coords(ratio_pad): (h0, w0, gain, pad_w,
+ * pad_h).  iouv: host array of niou <= 16 ascending IoU thresholds (torch.linspace(0.5, 0.95, 10) as fp32).
+ * A label becomes native pixels in fp32 in the reference's order: (x, y, w, h) * (canvas_w, canvas_h, canvas_w,
+ * canvas_h), x -+ w / 2, minus the pad, IEEE division by gain, clamp to [0, w0] / [0, h0].  Each row
+ * r < count[b] takes the label of its class (float equality with det[r,5]) of highest box_iou, the first one
+ * on ties (torch.max); a NaN among them gives none.  A row whose best IoU exceeds iouv[0] claims its label; a
+ * label goes to the lowest such row and every other row that chose it gets nothing (test.py:202-210).
+ * correct [B,max_det,niou] uint8: best > iouv[:] for the winners, 0 elsewhere (rows >= count[b] included);
+ * claimed_by [L] int32: the winning row of each label, or -1.  Both are written in full. */
+int yv7_match(const float* det, const int32_t* count, int B, int max_det, const float* targets,
+              const int32_t* label_off, int L, const yv7_scale_desc* images, int canvas_h, int canvas_w,
+              const float* iouv, int niou, uint8_t* correct, int32_t* claimed_by, void* stream);
 
 #ifdef __cplusplus
 }

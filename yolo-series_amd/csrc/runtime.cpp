@@ -1,5 +1,6 @@
 // libyv7 runtime: the C ABI of include/yv7.h outside the plan — version and error reporting, NMS, the
-// End2End output mode, the letterbox (one size or ragged) and the boxes' way back to image pixels.
+// End2End output mode, the letterbox (one size or ragged), the boxes' way back to image pixels and the
+// matching of predictions to labels.
 // (Plans: plan_create.cpp, plan_layout.cpp, forward.cpp.)
 #include <cmath>
 
@@ -166,6 +167,32 @@ int yv7_scale_boxes(float* det, const int32_t* count, int B, int max_det, const 
   hipError_t e = yv7::launch_scale_boxes(det, count, B, max_det, reinterpret_cast<const yv7::ScaleImage*>(images),
                                          round_boxes != 0, xywh, xyxyn, xywhn, reinterpret_cast<hipStream_t>(stream));
   if (e != hipSuccess) return hip_fail(e, "yv7_scale_boxes launch");
+  return 0;
+}
+
+int yv7_match(const float* det, const int32_t* count, int B, int max_det, const float* targets,
+              const int32_t* label_off, int L, const yv7_scale_desc* images, int canvas_h, int canvas_w,
+              const float* iouv, int niou, uint8_t* correct, int32_t* claimed_by, void* stream) {
+  if (B <= 0) return fail(YV7_E_ARG, "yv7_match: B must be positive");
+  if (max_det <= 0) return fail(YV7_E_ARG, "yv7_match: max_det must be positive");
+  if (niou < 1 || niou > yv7::MATCH_MAX_IOU) return fail(YV7_E_ARG, "yv7_match: niou must be in 1..16");
+  if (L < 0) return fail(YV7_E_ARG, "yv7_match: L must not be negative");
+  if (L > 0 && !targets) return fail(YV7_E_ARG, "yv7_match: null targets with L > 0");
+  if (!det || !count || !label_off || !images || !iouv || !correct || (L > 0 && !claimed_by))
+    return fail(YV7_E_ARG, "yv7_match: null argument");
+  if (canvas_h <= 0 || canvas_w <= 0) return fail(YV7_E_ARG, "yv7_match: canvas must be positive");
+  for (int i = 0; i < B; ++i) {
+    const std::string who = "yv7_match: image " + std::to_string(i);
+    if (images[i].h0 <= 0 || images[i].w0 <= 0) return fail(YV7_E_ARG, who + " has a non-positive size");
+    if (!(images[i].gain > 0.f) || !std::isfinite(images[i].gain))
+      return fail(YV7_E_ARG, who + ": gain must be positive and finite");
+  }
+  yv7::MatchIou th;
+  for (int k = 0; k < yv7::MATCH_MAX_IOU; ++k) th.v[k] = iouv[std::min(k, niou - 1)];
+  hipError_t e = yv7::launch_match(det, count, B, max_det, targets, label_off, L,
+                                   reinterpret_cast<const yv7::ScaleImage*>(images), canvas_h, canvas_w, th, niou,
+                                   correct, claimed_by, reinterpret_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return hip_fail(e, "yv7_match launch");
   return 0;
 }
 

@@ -357,5 +357,13 @@ hipError_t launch_scale_boxes(float* det, const int32_t* count, int B, int max_d
                               int round_boxes, float* xywh, float* xyxyn, float* xywhn, hipStream_t st);
 hipError_t launch_end2end_pack(const float* det, const int32_t* count, int B, int max_det, int topk,
                                int32_t* num_dets, float* boxes, float* scores, int32_t* classes, hipStream_t st);
+// evaluate.hip: the IoU thresholds travel by value too
+constexpr int MATCH_MAX_IOU = 16;
+struct MatchIou {
+  float v[MATCH_MAX_IOU];
+};
+hipError_t launch_match(const float* det, const int32_t* count, int B, int max_det, const float* targets,
+                        const int32_t* label_off, int L, const ScaleImage* images, int canvas_h, int canvas_w,
+                        const MatchIou& iouv, int niou, uint8_t* correct, int32_t* claimed_by, hipStream_t st);
 
 }  // namespace yv7

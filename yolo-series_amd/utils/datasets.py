@@ -9,8 +9,18 @@ writes the [B, 3, S, S] model input in one launch; `letterbox_ragged(frames, geo
 so for frames of different sizes (yv7_letterbox_ragged), with `autoshape_geometry` supplying autoShape's
 inference shape and per-frame geometry (models/common.py:909-915).  There is no CPU path: inputs go to the current
 HIP device and the library must be built (the ctypes binding raises otherwise).
+
+`create_dataloader` / `LoadImagesAndLabels` restate the non-augmented path of the reference's validation loader
+(utils/datasets.py:68-96, 352-490, 826-929, 959-971) for the plain images/ + labels/*.txt layout: the image
+list, label files, rectangular batch shapes, per-image geometry, label transform and `shapes` are the
+reference's; the pixels are decoded on the host and written onto the batch's canvas by one letterbox_ragged call.
 """
 from __future__ import annotations
+
+import glob
+import os
+from concurrent.futures import ThreadPoolExecutor
+from pathlib import Path
 
 import numpy as np
 import torch
@@ -215,3 +225,228 @@ class LoadImages:
 
     def __len__(self):
         return self.nf
+
+
+# ------------------------------------------------------------------------------------------ validation set
+LOADER_WORKERS = 8     # host decode threads: a fixed default, never sized from the machine's CPU count
+
+
+def img2label_paths(img_paths):
+    """datasets.py:352-355: .../images/x.jpg -> .../labels/x.txt (the first /images/ and the last extension)."""
+    sa, sb = os.sep + 'images' + os.sep, os.sep + 'labels' + os.sep
+    out = []
+    for p in img_paths:
+        q = p.replace(sa, sb, 1)
+        out.append('txt'.join(q.rsplit(q.split('.')[-1], 1)))
+    return out
+
+
+def read_label_file(path):
+    """datasets.py:612-631 for one label file: fp32 [n, 5] rows (cls, x, y, w, h), normalised.  A missing or
+    empty file is an empty label set; a malformed row raises ValueError naming the file (the reference drops the
+    image with a warning); duplicate rows are dropped, the first of each staying in file order."""
+    if not os.path.isfile(path):
+        return np.zeros((0, 5), dtype=np.float32)
+    with open(path) as f:
+        rows = [ln.split() for ln in f.read().strip().splitlines()]
+    if not rows:
+        return np.zeros((0, 5), dtype=np.float32)
+    if any(len(r) != 5 for r in rows):
+        raise ValueError(f'{path}: labels require 5 columns each')
+    try:
+        l = np.array(rows, dtype=np.float32)
+    except ValueError as e:
+        raise ValueError(f'{path}: {e}') from None
+    if not (l >= 0).all():       # a NaN fails this too
+        raise ValueError(f'{path}: negative labels')
+    if not (l[:, 1:] <= 1).all():
+        raise ValueError(f'{path}: non-normalized or out of bounds coordinate labels')
+    _, first = np.unique(l, axis=0, return_index=True)
+    return l[np.sort(first)]
+
+
+def list_images(path, prefix=''):
+    """datasets.py:383-398: the sorted image files under a directory (recursively), or named by a .txt list whose
+    './' entries are relative to the list; several of either as a list."""
+    f = []
+    for p in path if isinstance(path, (list, tuple)) else [path]:
+        p = Path(p)
+        if p.is_dir():
+            f += glob.glob(str(p / '**' / '*.*'), recursive=True)
+        elif p.is_file():
+            parent = str(p.parent) + os.sep
+            with open(p) as t:
+                f += [parent + x[2:] if x.startswith('./') else x for x in t.read().strip().splitlines()]
+        else:
+            raise Exception(f'{prefix}Error loading data from {path}: {p} does not exist')
+    files = sorted(x.replace('/', os.sep) for x in f if x.split('.')[-1].lower() in IMG_FORMATS)
+    assert files, f'{prefix}No images found in {path}'
+    return files
+
+
+def image_size(path):
+    """(w, h) from the file's header, without decoding: the size imread() returns (EXIF orientation is not applied
+    by either)."""
+    from PIL import Image
+    with Image.open(path) as im:
+        return im.size
+
+
+class LoadImagesAndLabels:
+    """The reference's LoadImagesAndLabels (datasets.py:358-958) without augmentation, mosaic, label cache,
+    segments or its CrowdHuman / SHEL modes.  Holds, per image in evaluation order: img_files, label_files,
+    labels (fp32 [n, 5], normalised to the image) and shapes ((w, h), float64); with rect, batch_shapes (h, w)."""
+
+    def __init__(self, path, img_size=640, batch_size=16, augment=False, hyp=None, rect=False, cache_images=False,
+                 single_cls=False, stride=32, pad=0.0, prefix=''):
+        if augment:
+            raise NotImplementedError('augmented loading (training) is not part of the MI355X inference path')
+        self.img_size, self.augment, self.hyp, self.rect, self.stride, self.path = img_size, False, hyp, rect, stride, path
+        self.img_files = list_images(path, prefix)
+        self.label_files = img2label_paths(self.img_files)
+        self.labels = [read_label_file(f) for f in self.label_files]
+        self.shapes = np.array([image_size(f) for f in self.img_files], dtype=np.float64)   # wh
+        if single_cls:       # datasets.py:452-454
+            for x in self.labels:
+                x[:, 0] = 0
+        n = len(self.img_files)
+        bi = np.floor(np.arange(n) / batch_size).astype(int)     # batch index of image, datasets.py:460-464
+        nb = bi[-1] + 1
+        self.batch, self.n, self.indices, self.batch_size = bi, n, range(n), batch_size
+        if rect:             # datasets.py:467-490
+            ar = self.shapes[:, 1] / self.shapes[:, 0]           # h / w
+            irect = ar.argsort()
+            self.img_files = [self.img_files[i] for i in irect]
+            self.label_files = [self.label_files[i] for i in irect]
+            self.labels = [self.labels[i] for i in irect]
+            self.shapes = self.shapes[irect]
+            ar = ar[irect]
+            shapes = [[1, 1]] * nb
+            for i in range(nb):
+                ari = ar[bi == i]
+                mini, maxi = ari.min(), ari.max()
+                if maxi < 1:
+                    shapes[i] = [maxi, 1]
+                elif mini > 1:
+                    shapes[i] = [1, 1 / mini]
+            self.batch_shapes = np.ceil(np.array(shapes) * img_size / stride + pad).astype(int) * stride
+        self.imgs = [None] * n   # decoded frames stay here when cache_images
+        self.cache_images = bool(cache_images)
+
+    def __len__(self):
+        return self.n
+
+    def canvas(self, index):
+        """(h, w) of the letterboxed batch image `index` lands in (datasets.py:854)."""
+        if self.rect:
+            return tuple(int(v) for v in self.batch_shapes[self.batch[index]])
+        return (self.img_size, self.img_size)
+
+    def geometry(self, index):
+        """load_image's sizes (datasets.py:966-971) followed by letterbox(auto=False, scaleup=False)
+        (datasets.py:855, 1277-1307): ((h0, w0), (h, w), letterbox_geometry of (h, w) on the canvas)."""
+        w0, h0 = (int(v) for v in self.shapes[index])
+        r = self.img_size / max(h0, w0)
+        h, w = (int(h0 * r), int(w0 * r)) if r != 1 else (h0, w0)
+        return (h0, w0), (h, w), letterbox_geometry((h, w), self.canvas(index), auto=False, scaleup=False)
+
+    def item_shapes(self, index):
+        """The reference's `shapes` entry (datasets.py:856): ((h0, w0), ((h / h0, w / w0), (dw, dh)))."""
+        (h0, w0), (h, w), (_, _, pad, _) = self.geometry(index)
+        return (h0, w0), ((h / h0, w / w0), pad)
+
+    def item_labels(self, index):
+        """The image's labels on its canvas (datasets.py:858-860, 894-899): fp32 [n, 5] (cls, x, y, w, h)
+        normalised by the canvas, in the reference's numpy fp32 arithmetic."""
+        _, (h, w), (_, ratio, (padw, padh), _) = self.geometry(index)
+        ch, cw = self.canvas(index)
+        x = self.labels[index]
+        l = x.copy()
+        if l.size:
+            sw, sh = ratio[0] * w, ratio[1] * h
+            x1 = sw * (x[:, 1] - x[:, 3] / 2) + padw    # xywhn2xyxy, general.py:295-302
+            y1 = sh * (x[:, 2] - x[:, 4] / 2) + padh
+            x2 = sw * (x[:, 1] + x[:, 3] / 2) + padw
+            y2 = sh * (x[:, 2] + x[:, 4] / 2) + padh
+            l[:, 1], l[:, 2], l[:, 3], l[:, 4] = (x1 + x2) / 2, (y1 + y2) / 2, x2 - x1, y2 - y1   # xyxy2xywh
+            l[:, [2, 4]] /= ch
+            l[:, [1, 3]] /= cw
+        return l
+
+    def frame(self, index):
+        """The decoded image: HWC BGR uint8 at its own size."""
+        img = self.imgs[index]
+        if img is None:
+            img = imread(self.img_files[index])
+            if self.cache_images:
+                self.imgs[index] = img
+        return img
+
+
+class ValLoader:
+    """Batches of a LoadImagesAndLabels in order, as the reference's DataLoader + collate_fn yield them
+    (datasets.py:925-929): (img, targets, paths, shapes), with img the letterboxed batch already on the device
+    as [nb, 3, h, w] half (or float) RGB in [0, 1] and targets fp32 [n, 6] (index in batch, cls, x, y, w, h) on
+    the host.  Frames are decoded by a thread pool one batch ahead, uploaded through pinned memory and written
+    onto the canvas (colour 114) by one letterbox_ragged call on the current stream."""
+
+    def __init__(self, dataset, batch_size, half=True, device=None, workers=LOADER_WORKERS):
+        self.dataset, self.batch_size, self.half, self.device = dataset, batch_size, half, device
+        self.workers = max(1, int(workers))
+
+    def __len__(self):
+        return (len(self.dataset) + self.batch_size - 1) // self.batch_size
+
+    def __iter__(self):
+        for img, targets, paths, shapes, _ in self.batches():
+            yield img, targets, paths, shapes
+
+    def _upload(self, frames, device):
+        sizes = [f.size for f in frames]
+        host = torch.empty(sum(sizes), dtype=torch.uint8, pin_memory=True)
+        view, off = host.numpy(), 0
+        for f, n in zip(frames, sizes):
+            view[off:off + n] = f.reshape(-1)
+            off += n
+        dev = host.to(device, non_blocking=True)
+        out, off = [], 0
+        for f, n in zip(frames, sizes):
+            out.append(dev[off:off + n].view(f.shape))
+            off += n
+        return out
+
+    def batches(self):
+        """As __iter__, with each batch's per-image label counts as a fifth entry."""
+        ds = self.dataset
+        device = _hip_device(self.device if self.device is not None else 'cuda')
+        groups = [range(i, min(i + self.batch_size, len(ds))) for i in range(0, len(ds), self.batch_size)]
+        with ThreadPoolExecutor(max_workers=self.workers) as pool:
+            ahead = [pool.submit(ds.frame, i) for i in groups[0]] if groups else []
+            for g, idx in enumerate(groups):
+                frames = [f.result() for f in ahead]
+                ahead = [pool.submit(ds.frame, i) for i in groups[g + 1]] if g + 1 < len(groups) else []
+                geoms = [ds.geometry(i)[2] for i in idx]
+                img = letterbox_ragged(self._upload(frames, device), geoms, ds.canvas(idx[0]), swap_rb=True,
+                                       out_kind=OUT_F16_CHW if self.half else OUT_F32_CHW, device=device)
+                labels = [ds.item_labels(i) for i in idx]
+                targets = torch.zeros((sum(len(l) for l in labels), 6))
+                off = 0
+                for j, l in enumerate(labels):
+                    targets[off:off + len(l), 0] = j
+                    targets[off:off + len(l), 1:] = torch.from_numpy(l)
+                    off += len(l)
+                yield (img, targets, tuple(ds.img_files[i] for i in idx), tuple(ds.item_shapes(i) for i in idx),
+                       [len(l) for l in labels])
+
+
+def create_dataloader(mode, path, imgsz, batch_size, stride, opt=None, hyp=None, augment=False, cache=False, pad=0.0,
+                      rect=False, rank=-1, world_size=1, workers=LOADER_WORKERS, image_weights=False, quad=False,
+                      prefix='', dataset_name='COCO2017', data_dict=None, half=True, device=None):
+    """datasets.py:68-96 for evaluation: (loader, dataset); both support len().  mode, rank, world_size,
+    image_weights, quad, dataset_name and data_dict are accepted for the reference's call sites and unused."""
+    if augment:
+        raise NotImplementedError('augmented loading (training) is not part of the MI355X inference path')
+    dataset = LoadImagesAndLabels(path, imgsz, batch_size, augment=False, hyp=hyp, rect=rect, cache_images=cache,
+                                  single_cls=bool(getattr(opt, 'single_cls', False)), stride=int(stride), pad=pad,
+                                  prefix=prefix)
+    return ValLoader(dataset, min(batch_size, len(dataset)), half=half, device=device, workers=workers), dataset

@@ -5,11 +5,15 @@ runs the whole batch as HIP kernels (libyv7 yv7_nms: candidate filter, conf prod
 multi-label expansion, class filter, class-offset boxes, stable score sort, greedy IoU
 suppression, max_det) in one stream-ordered call; the only host sync is reading the per-image
 counts to build the returned list, exactly where the reference's semantics need it.
-The small box helpers below are plain tensor math on the caller's device.
+The small box helpers below are plain tensor math on the caller's device; check_dataset, check_file,
+increment_path and coco80_to_coco91_class are test.py's host-side helpers.
 """
 from __future__ import annotations
 
+import glob
 import math
+import re
+from pathlib import Path
 
 import torch
 
@@ -29,6 +33,37 @@ def check_img_size(img_size, s=32):  # general.py:124-129
     if new_size != img_size:
         print('WARNING: --img-size %g must be multiple of max stride %g, updating to %g' % (img_size, s, new_size))
     return new_size
+
+
+def check_file(file):  # general.py:146-154
+    if file == '' or Path(file).is_file():
+        return file
+    found = glob.glob('./**/' + file, recursive=True)
+    assert len(found), f'File Not Found: {file}'
+    assert len(found) == 1, f"Multiple files match '{file}', specify exact path: {found}"
+    return found[0]
+
+
+def check_dataset(data):  # general.py:157-174, local paths only: a missing dataset is an error, never a download
+    val = data.get('val')
+    if val and len(val):
+        missing = [str(p) for p in (Path(x).resolve() for x in (val if isinstance(val, list) else [val]))
+                   if not p.exists()]
+        if missing:
+            raise Exception(f'Dataset not found, nonexistent paths: {missing} (this package does not download)')
+
+
+def increment_path(path, exist_ok=True, sep=''):  # general.py:902-912: runs/exp -> runs/exp2, runs/exp3, ...
+    path = Path(path)
+    if not path.exists() or exist_ok:
+        return str(path)
+    taken = [re.search(rf'{re.escape(path.stem)}{sep}(\d+)', d) for d in glob.glob(f'{path}{sep}*')]
+    taken = [int(m.group(1)) for m in taken if m]
+    return f'{path}{sep}{max(taken) + 1 if taken else 2}'
+
+
+def coco80_to_coco91_class():  # general.py:244-253: the 80 contiguous class indices as COCO's paper ids
+    return [i for i in range(1, 91) if i not in (12, 26, 29, 30, 45, 66, 68, 69, 71, 83)]
 
 
 def xyxy2xywh(x):  # general.py:256-263

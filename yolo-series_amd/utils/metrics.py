@@ -9,8 +9,12 @@ Mirrors the reference's test.py statistics and utils/metrics.py:
   ap_per_class       utils/metrics.py:18-78   (host numpy, as the reference)
   compute_ap         utils/metrics.py:81-110  (101-point interpolation, v5_metric=False sentinel)
   map_from_lists     test.py:218-227          mAP@0.5 and mAP@0.5:0.95 over a set of images
+  match_batch        test.py:123,131,179-213  the matching for a whole batch in one launch (libyv7 yv7_match),
+                     stream-ordered, on nms_batched's output after scale_boxes: what test.py's loop runs
 """
 from __future__ import annotations
+
+import ctypes
 
 import numpy as np
 import torch
@@ -51,6 +55,44 @@ def match_predictions(pred, labels, iouv=None):
     win = valid & (first[tgt] == idx)
     correct[win] = best[win, None] > iouv
     return correct
+
+
+def match_batch(det, count, targets, label_off, descs, canvas_hw, iouv=None):
+    """test.py:123,131,179-213 for a batch, stream-ordered (libyv7 yv7_match): det [B,max_det,6] and count [B]
+    int32 as nms_batched returns them AFTER scale_boxes (native pixels); targets [L,6] fp32 on the device, rows
+    (image, cls, x, y, w, h) normalised to the canvas and sorted by image; label_off [B+1] int32 on the device,
+    image b's rows being label_off[b]:label_off[b+1]; descs one scale_desc per image (for ratio_pad:
+    (h0, w0, ratio[0], pad_w, pad_h)); canvas_hw the model input's (h, w).
+    Returns (correct [B,max_det,niou] uint8, zero in rows >= count[b]; claimed_by [L] int32, the row that
+    took each label or -1)."""
+    from yv7 import _lib
+    if not det.is_cuda:
+        raise RuntimeError('match_batch runs on a ROCm device (libyv7); got a CPU tensor')
+    B, max_det, six = det.shape
+    dev = det.device
+    if det.dtype != torch.float32 or six != 6 or not det.is_contiguous() or len(descs) != B:
+        raise ValueError(f'match_batch: expected contiguous fp32 det [B, max_det, 6] and {B} descriptors')
+    if count.dtype != torch.int32 or count.numel() != B or count.device != dev or not count.is_contiguous():
+        raise ValueError('match_batch: count must be contiguous int32 [B] on det\'s device')
+    if (targets.dtype != torch.float32 or targets.dim() != 2 or targets.shape[1] != 6 or not targets.is_contiguous()
+            or targets.device != dev):
+        raise ValueError('match_batch: targets must be contiguous fp32 [L, 6] on det\'s device')
+    if (label_off.dtype != torch.int32 or label_off.numel() != B + 1 or label_off.device != dev
+            or not label_off.is_contiguous()):
+        raise ValueError('match_batch: label_off must be contiguous int32 [B + 1] on det\'s device')
+    iouv = iou_thresholds() if iouv is None else iouv
+    th = [float(v) for v in iouv.detach().float().cpu().tolist()]
+    n_l, niou = targets.shape[0], len(th)
+    arr = (_lib.ScaleDesc * B)(*[_lib.ScaleDesc(*d) for d in descs])
+    correct = torch.empty((B, max_det, niou), dtype=torch.uint8, device=dev)
+    claimed_by = torch.empty((n_l,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib.lib().yv7_match(det.data_ptr(), count.data_ptr(), B, max_det, targets.data_ptr() if n_l else None,
+                                  label_off.data_ptr(), n_l, arr, int(canvas_hw[0]), int(canvas_hw[1]),
+                                  (ctypes.c_float * niou)(*th), niou, correct.data_ptr(),
+                                  claimed_by.data_ptr() if n_l else None, torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(rc, 'yv7_match')
+    return correct, claimed_by
 
 
 def compute_ap(recall, precision, v5_metric=False):
