@@ -27,6 +27,8 @@
  *                     .round(), the Detections views            models/common.py:940-948
  *   yv7_match         the per-image, per-class matching of      test.py:123,131,179-213
  *                     predictions to labels for mAP
+ *   yv7_confusion     ConfusionMatrix.process_batch over a      utils/metrics.py:121-159 as called from
+ *                     batch, into a matrix kept on the device   test.py:137-140,181-189
  */
 #ifndef YV7_H
 #define YV7_H
@@ -278,6 +280,31 @@ int yv7_scale_boxes(float* det, const int32_t* count, int B, int max_det, const 
 int yv7_match(const float* det, const int32_t* count, int B, int max_det, const float* targets,
               const int32_t* label_off, int L, const yv7_scale_desc* images, int canvas_h, int canvas_w,
               const float* iouv, int niou, uint8_t* correct, int32_t* claimed_by, void* stream);
+
+/* The evaluation's confusion matrix (replaces ConfusionMatrix.process_batch, utils/metrics.py:121-159, as test.py
+ * calls it per image at :188-189 with its two skips at :137-140 and :181), for a whole batch in one launch per 64
+ * images and without a host sync.  det, count, targets, label_off, images, canvas_h, canvas_w: exactly yv7_match's,
+ * and a label becomes native pixels by the same arithmetic.  All inputs are read-only; count and label_off are
+ * clamped on the device.
+ * matrix: device int32, (nc + 1) * (nc + 1) + 1 entries, row-major [row][col], 1 <= nc <= 1024.  The call ADDS
+ * into it and never zeroes it: the caller zeroes it once per evaluation.  The last entry counts dropped increments.
+ * ws: device scratch of at least yv7_confusion_ws_bytes(B, max_det, L) bytes, 8-byte aligned (per-label bids and
+ * per-row choices: neither max_det nor the labels per image are limited).
+ * Per image b: nothing is added if count[b] == 0 or the image has no labels.  Rows r < count[b] with
+ * det[r,4] > conf (strict, fp32) are live.  box_iou in fp32 between every label and every live row, classes
+ * playing no part; a pair is a candidate iff iou > iou_thres (strict; a NaN never is).  Each live row keeps its
+ * candidate label of highest IoU; each label keeps, among the rows that chose it, the row of highest IoU: those
+ * pairs are the matches, and a row whose label went to another row is unmatched (it takes no second choice).
+ * With gc the label's class and dc the row's: a matched label adds 1 at [gc][dc], an unmatched label at [nc][gc];
+ * if the image has at least one match every unmatched live row adds 1 at [dc][nc], otherwise the rows add nothing
+ * (the reference's `if n:`).  A class is its float truncated toward zero; outside [0, nc) or NaN, that increment
+ * is dropped and the last entry is incremented instead.
+ * Ties, which the reference leaves to an unstable argsort: a row takes the first maximum in label order, a label
+ * takes the lowest row index.  The sums are integers: identical from run to run. */
+size_t yv7_confusion_ws_bytes(int B, int max_det, int L);
+int yv7_confusion(const float* det, const int32_t* count, int B, int max_det, const float* targets,
+                  const int32_t* label_off, int L, const yv7_scale_desc* images, int canvas_h, int canvas_w,
+                  float conf, float iou_thres, int nc, int32_t* matrix, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,12 +1,14 @@
-"""Measurements for the batched mAP evaluation (DESIGN §4.19), one process, one box:
+"""Measurements for the batched mAP evaluation (DESIGN §4.19, §4.20), one process, one box:
 
   (a) per batch of 32, yolov7 640, synthetic weights, conf 0.001, iou 0.65: device time (event pairs) of the eval
-      NMS (multi_label), scale_boxes and yv7_match;
+      NMS (multi_label), scale_boxes, yv7_match and yv7_confusion (ConfusionMatrix.process_batches);
   (b) host time from the NMS output to that batch's appended statistics: the per-image way (non_max_suppression's
       list, then per image scale_coords + metrics.match_predictions + .cpu()) against the batched step
       (scale_boxes + match_batch + pinned copies + one event wait + slicing), old and new alternating;
-  (c) test() images/s on an in-memory dataset of pre-decoded frames against forward + eval NMS alone on the same
-      batches.
+  (c) test() images/s on an in-memory dataset of pre-decoded frames, plots=True (the confusion launch in every
+      batch step) and plots=False alternating, against forward + eval NMS alone on the same batches; and the
+      seconds the five plot files take after the loop (ap_per_class(plot=True) beyond plot=False, and
+      ConfusionMatrix.plot with its one read of the device matrix).
 
     python scripts/eval_profile.py --out profiles/evaluate
 """
@@ -87,8 +89,9 @@ def measure_ab(model, dev, a):
     shapes = [((S, S), ((1.0, 1.0), (0.0, 0.0)))] * B
 
     # (a) device times
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
-    dev_ms = {'nms': [], 'scale_boxes': [], 'match': []}
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
+    dev_ms = {'nms': [], 'scale_boxes': [], 'match': [], 'confusion': []}
+    cm = M.ConfusionMatrix(nc=80)
     for it in range(a.warmup + a.reps):
         off = T.label_offsets(t_dev, B, counts)
         ev[0].record()
@@ -98,6 +101,8 @@ def measure_ab(model, dev, a):
         ev[2].record()
         M.match_batch(det, cnt, t_dev, off, descs, (S, S), iouv)
         ev[3].record()
+        cm.process_batches(det, cnt, t_dev, off, descs, (S, S))
+        ev[4].record()
         torch.cuda.synchronize()
         if it >= a.warmup:
             for k, name in enumerate(dev_ms):
@@ -158,8 +163,13 @@ def measure_ab(model, dev, a):
             enq_s.append(te * 1e3)
     same = all(np.array_equal(x[0], y[0]) and np.array_equal(x[1], y[1]) and np.array_equal(x[2], y[2])
                for x, y in zip(so, sn)) and len(so) == len(sn)
+    live = int((torch.arange(det.shape[1], device=dev)[None] < cnt[:, None]).logical_and(det[..., 4] > cm.conf).sum())
+    matrix = cm.matrix
     return {'batch': B, 'img': S, 'conf': a.conf, 'iou': a.iou, 'labels': int(targets.shape[0]),
             'detections_kept': int(sum(kept)), 'device_ms': {k: spread(v) for k, v in dev_ms.items()},
+            'confusion': {'conf': cm.conf, 'iou_thres': cm.iou_thres, 'live_rows_per_batch': live,
+                          'increments_per_batch': float(matrix.sum()) / (a.warmup + a.reps),
+                          'matched_per_batch': float(matrix[:80, :80].sum()) / (a.warmup + a.reps)},
             'host_ms_per_batch': {'per_image': spread(old_s), 'batched': spread(new_s),
                                   'batched_enqueue_only': spread(enq_s)},
             'per_image_and_batched_statistics_equal': bool(same)}
@@ -193,16 +203,51 @@ def measure_c(model, dev, a):
         torch.cuda.synchronize()
         data = {'nc': 80, 'val': tmp}
 
-        def full():
+        def full(plots, **kw):
+            # with a model and the default save_dir no file is written: plots=True times the loop with the
+            # confusion launch in it, the plotting is timed on its own below
             with contextlib.redirect_stdout(io.StringIO()):
                 torch.cuda.synchronize()
                 t = time.perf_counter()
                 T.test(data, model=model, dataloader=loader, batch_size=a.batch, imgsz=a.img, conf_thres=a.conf,
-                       iou_thres=a.iou)
+                       iou_thres=a.iou, plots=plots, **kw)
                 torch.cuda.synchronize()
                 dt = time.perf_counter() - t
             model.half()   # test() leaves the model in fp32 like the reference
             return len(ds) / dt
+
+        def plotting_seconds():
+            """One run that writes confusion_matrix.png, timed where test() makes the call (the device matrix is
+            read there); and the four curve files on seeded statistics of this set's size (its labels are random,
+            so its own statistics hold no true positive and test() skips ap_per_class, as the reference does)."""
+            from utils import metrics as M
+            spent = {}
+            real_cm = T.ConfusionMatrix
+
+            class TimedMatrix(real_cm):
+                def plot(self, *args, **kw):
+                    t = time.perf_counter()
+                    super().plot(*args, **kw)
+                    spent['confusion_matrix_plot'] = time.perf_counter() - t
+            T.ConfusionMatrix = TimedMatrix
+            try:
+                with tempfile.TemporaryDirectory() as out:
+                    full(True, save_dir=out)
+                    rng = np.random.default_rng(4)
+                    n = len(ds) * G.MAX_DET
+                    conf = rng.random(n).astype(np.float32)
+                    stats = (rng.random((n, 10)) < conf[:, None] * np.linspace(1.0, 0.3, 10), conf,
+                             rng.integers(0, 80, n).astype(np.float32),
+                             rng.integers(0, 80, len(ds) * 8).astype(np.float32))
+                    names = {i: str(i) for i in range(80)}
+                    for key, plot in (('ap_per_class_no_plot', False), ('ap_per_class_plot', True)):
+                        t = time.perf_counter()
+                        M.ap_per_class(*stats, plot=plot, save_dir=out, names=names)
+                        spent[key] = time.perf_counter() - t
+                    spent['files'] = sorted(os.listdir(out))
+            finally:
+                T.ConfusionMatrix = real_cm
+            return spent
 
         def forward_nms():
             torch.cuda.synchronize()
@@ -221,14 +266,19 @@ def measure_c(model, dev, a):
             torch.cuda.synchronize()
             return len(ds) / (time.perf_counter() - t)
 
-        full(), forward_nms()
-        ev, fw, lo = [], [], []
+        full(True), full(False), forward_nms()
+        ev, ev_off, fw, lo = [], [], [], []
         for _ in range(a.passes):
             fw.append(forward_nms())
-            ev.append(full())
+            ev.append(full(True))
+            ev_off.append(full(False))
             lo.append(loader_only())
+        plotting = plotting_seconds()
     return {'images': len(ds), 'frame': [480, 640], 'canvas': [int(v) for v in ds.batch_shapes[0]], 'batch': a.batch,
-            'conf': a.conf, 'iou': a.iou, 'test_images_per_s': spread(ev), 'forward_nms_images_per_s': spread(fw),
+            'conf': a.conf, 'iou': a.iou, 'test_images_per_s': spread(ev),
+            'test_plots_false_images_per_s': spread(ev_off),
+            'ratio_plots_true_over_false': statistics.median(ev) / statistics.median(ev_off),
+            'plotting_seconds': plotting, 'forward_nms_images_per_s': spread(fw),
             'loader_alone_images_per_s': spread(lo),
             'ratio_test_over_forward_nms': statistics.median(ev) / statistics.median(fw)}
 

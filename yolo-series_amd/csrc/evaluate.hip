@@ -15,6 +15,10 @@
 // label with an unsigned atomic min of its row index on claimed_by, in global memory, so labels per image are
 // unbounded.  -1 is the largest unsigned value: "unclaimed" needs no second pass.  After a barrier a row has
 // won iff its label still holds its index: rows of later batches are larger and cannot take a label back.
+//
+// confusion_kernel (below match_kernel) builds the evaluation's confusion matrix, utils/metrics.py:121-159 as
+// test.py:137-140,181-189 calls it, for a whole batch in one launch behind match_kernel's, adding into a matrix
+// that stays on the device for the whole run.  It shares native_label() with match_kernel.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -38,6 +42,22 @@ __device__ __forceinline__ float tmin(float a, float b) { return (a != a || b !=
 __device__ __forceinline__ float tmax(float a, float b) { return (a != a || b != b) ? a + b : fmaxf(a, b); }
 // Tensor.clamp(0)
 __device__ __forceinline__ float clamp0(float a) { return a != a ? a : fmaxf(a, 0.f); }
+
+// One label row (image, class, x, y, w, h normalised to the canvas) as its box in the image's own pixels:
+// test.py:123 (to canvas pixels), xywh2xyxy, then scale_coords(ratio_pad) + clip_coords
+struct NativeBox {
+  float x1, y1, x2, y2;
+};
+__device__ __forceinline__ NativeBox native_label(const float* __restrict__ t, float canvas_w, float canvas_h,
+                                                  const ScaleImage& im, float w0, float h0) {
+  const float x = t[2] * canvas_w, y = t[3] * canvas_h, w = t[4] * canvas_w, h = t[5] * canvas_h;
+  NativeBox n;
+  n.x1 = fminf(fmaxf(((x - w / 2.f) - im.pad_w) / im.gain, 0.f), w0);
+  n.y1 = fminf(fmaxf(((y - h / 2.f) - im.pad_h) / im.gain, 0.f), h0);
+  n.x2 = fminf(fmaxf(((x + w / 2.f) - im.pad_w) / im.gain, 0.f), w0);
+  n.y2 = fminf(fmaxf(((y + h / 2.f) - im.pad_h) / im.gain, 0.f), h0);
+  return n;
+}
 
 __global__ __launch_bounds__(MATCH_THREADS) void match_kernel(
     MatchChunk ch, int b0, const float* __restrict__ det, const int32_t* __restrict__ count, int max_det,
@@ -81,14 +101,9 @@ __global__ __launch_bounds__(MATCH_THREADS) void match_kernel(
       __syncthreads();   // the previous chunk has been read
       if (c0 + tid < hi) {
         const float* t = targets + (size_t)(c0 + tid) * 6;
-        // test.py:123 (to canvas pixels), xywh2xyxy, then scale_coords(ratio_pad) + clip_coords
-        const float x = t[2] * canvas_w, y = t[3] * canvas_h, w = t[4] * canvas_w, h = t[5] * canvas_h;
-        const float x1 = fminf(fmaxf(((x - w / 2.f) - im.pad_w) / im.gain, 0.f), w0);
-        const float y1 = fminf(fmaxf(((y - h / 2.f) - im.pad_h) / im.gain, 0.f), h0);
-        const float x2 = fminf(fmaxf(((x + w / 2.f) - im.pad_w) / im.gain, 0.f), w0);
-        const float y2 = fminf(fmaxf(((y + h / 2.f) - im.pad_h) / im.gain, 0.f), h0);
-        s_cls[tid] = t[1]; s_x1[tid] = x1; s_y1[tid] = y1; s_x2[tid] = x2; s_y2[tid] = y2;
-        s_area[tid] = (x2 - x1) * (y2 - y1);
+        const NativeBox n = native_label(t, canvas_w, canvas_h, im, w0, h0);
+        s_cls[tid] = t[1]; s_x1[tid] = n.x1; s_y1[tid] = n.y1; s_x2[tid] = n.x2; s_y2[tid] = n.y2;
+        s_area[tid] = (n.x2 - n.x1) * (n.y2 - n.y1);
       }
       __syncthreads();
       if (live) {
@@ -120,7 +135,152 @@ __global__ __launch_bounds__(MATCH_THREADS) void match_kernel(
   }
 }
 
+// ------------------------------------------------------------------------------------------ confusion matrix
+// Per image (one workgroup), the reference's steps with its quirks: rows with conf > conf are live; every
+// (label, live row) pair of box_iou > iou_thres is a candidate, whatever the classes; a row keeps its candidate
+// label of highest IoU (the first maximum in label order), a label keeps among the rows that chose it the one of
+// highest IoU (the lowest row on ties), and a row that lost its label is unmatched: it takes no second choice.
+//
+// A row bids for its label with a 64-bit atomic max on key[label] = (IoU as an order-preserving unsigned word,
+// ~row): the higher IoU wins, then the lower row; 0 is "no bid" (no real IoU maps to a zero high word).  The
+// keys and each row's chosen label live in the workspace, so neither max_det nor the labels per image are bounded
+// by LDS.  After a barrier the labels add their cells (matched: [gc][dc], unmatched: [nc][gc]) and, if the image
+// has a match at all, the unmatched live rows add [dc][nc].  Cells are added with integer atomics, so the sums
+// do not depend on their order.
+__device__ __forceinline__ unsigned ordered_bits(float v) {
+  const unsigned u = __float_as_uint(v + 0.f);   // -0 becomes +0: equal floats, equal words
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// .int() of a class value as a matrix index, or -1 when it lies outside [0, nc) or is a NaN
+__device__ __forceinline__ int class_index(float c, int nc) {
+  return (c > -1.f && c < (float)nc) ? (int)c : -1;
+}
+
+// One increment at [r][c]; an index of -1 drops it and counts the drop in the entry behind the matrix
+__device__ __forceinline__ void add_cell(int32_t* matrix, int nc, int r, int c) {
+  const int n1 = nc + 1;
+  atomicAdd(matrix + ((r < 0 || c < 0) ? n1 * n1 : r * n1 + c), 1);
+}
+
+__global__ __launch_bounds__(MATCH_THREADS) void confusion_kernel(
+    MatchChunk ch, int b0, const float* __restrict__ det, const int32_t* __restrict__ count, int max_det,
+    const float* __restrict__ targets, const int32_t* __restrict__ label_off, int L, float canvas_h, float canvas_w,
+    float conf, float iou_thres, int nc, int32_t* matrix, unsigned long long* key, int32_t* chosen) {
+  __shared__ float s_x1[MATCH_THREADS], s_y1[MATCH_THREADS], s_x2[MATCH_THREADS], s_y2[MATCH_THREADS],
+      s_area[MATCH_THREADS];
+  __shared__ int s_any;
+  const int tid = threadIdx.x;
+  const ScaleImage im = ch.im[blockIdx.x];
+  const int b = b0 + blockIdx.x;
+  const int cnt = min(max(count[b], 0), max_det);
+  const int lo = min(max(label_off[b], 0), L);
+  const int hi = min(max(label_off[b + 1], lo), L);
+  if (cnt == 0 || hi == lo) return;   // test.py:137-140 and `if nl` (uniform over the workgroup)
+
+  if (tid == 0) s_any = 0;
+  for (int l = lo + tid; l < hi; l += MATCH_THREADS)
+    __hip_atomic_store(key + l, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __threadfence();
+  __syncthreads();
+
+  const float w0 = (float)im.w0, h0 = (float)im.h0;
+  const float* dimg = det + (size_t)b * max_det * 6;
+  int32_t* cimg = chosen + (size_t)b * max_det;
+  for (int r0 = 0; r0 < cnt; r0 += MATCH_THREADS) {
+    const int row = r0 + tid;
+    bool live = false;
+    float px1 = 0.f, py1 = 0.f, px2 = 0.f, py2 = 0.f, parea = 0.f;
+    if (row < cnt) {
+      const float* p = dimg + (size_t)row * 6;
+      live = p[4] > conf;
+      px1 = p[0]; py1 = p[1]; px2 = p[2]; py2 = p[3];
+      parea = (px2 - px1) * (py2 - py1);
+    }
+    bool found = false;
+    float best = 0.f;
+    int best_l = 0;
+    for (int c0 = lo; c0 < hi; c0 += MATCH_THREADS) {
+      __syncthreads();   // the previous chunk has been read
+      if (c0 + tid < hi) {
+        const NativeBox n = native_label(targets + (size_t)(c0 + tid) * 6, canvas_w, canvas_h, im, w0, h0);
+        s_x1[tid] = n.x1; s_y1[tid] = n.y1; s_x2[tid] = n.x2; s_y2[tid] = n.y2;
+        s_area[tid] = (n.x2 - n.x1) * (n.y2 - n.y1);
+      }
+      __syncthreads();
+      if (live) {
+        const int n = min(MATCH_THREADS, hi - c0);
+        for (int j = 0; j < n; ++j) {
+          // box_iou, utils/general.py:464-486
+          const float iw = clamp0(tmin(px2, s_x2[j]) - tmax(px1, s_x1[j]));
+          const float ih = clamp0(tmin(py2, s_y2[j]) - tmax(py1, s_y1[j]));
+          const float inter = iw * ih;
+          const float iou = inter / ((parea + s_area[j]) - inter);
+          if (iou > iou_thres && (!found || iou > best)) {   // a NaN is never a candidate
+            found = true;
+            best = iou;
+            best_l = c0 + j;
+          }
+        }
+      }
+    }
+    if (row < cnt) cimg[row] = found ? best_l : -1;
+    if (found)
+      atomicMax(key + best_l, ((unsigned long long)ordered_bits(best) << 32) | (0xffffffffu - (unsigned)row));
+  }
+  __threadfence();
+  __syncthreads();
+
+  bool any = false;
+  for (int l = lo + tid; l < hi; l += MATCH_THREADS) {
+    const unsigned long long k = __hip_atomic_load(key + l, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int gc = class_index(targets[(size_t)l * 6 + 1], nc);
+    if (k != 0ull) {
+      // the winner's row; a foreign key (label ranges that overlap through a bad label_off) stays in bounds
+      const unsigned row = min(0xffffffffu - (unsigned)k, (unsigned)(max_det - 1));
+      add_cell(matrix, nc, gc, class_index(dimg[(size_t)row * 6 + 5], nc));
+      any = true;
+    } else {
+      add_cell(matrix, nc, nc, gc);
+    }
+  }
+  if (any) s_any = 1;
+  __syncthreads();
+  if (!s_any) return;   // the reference's `if n:`: without a match the rows add nothing
+  for (int row = tid; row < cnt; row += MATCH_THREADS) {
+    const float* p = dimg + (size_t)row * 6;
+    if (!(p[4] > conf)) continue;
+    const int l = cimg[row];   // written by this very thread
+    unsigned winner = 0;   // ~row of the label's winner; no row's ~row is 0
+    if (l >= 0) winner = (unsigned)__hip_atomic_load(key + l, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const bool won = winner == 0xffffffffu - (unsigned)row;
+    if (!won) add_cell(matrix, nc, class_index(p[5], nc), nc);
+  }
+}
+
 }  // namespace
+
+size_t confusion_ws_bytes(int B, int max_det, int L) {
+  if (B <= 0 || max_det <= 0 || L < 0) return 0;
+  return (size_t)L * sizeof(unsigned long long) + (size_t)B * max_det * sizeof(int32_t);
+}
+
+hipError_t launch_confusion(const float* det, const int32_t* count, int B, int max_det, const float* targets,
+                            const int32_t* label_off, int L, const ScaleImage* images, int canvas_h, int canvas_w,
+                            float conf, float iou_thres, int nc, int32_t* matrix, void* ws, hipStream_t st) {
+  unsigned long long* key = reinterpret_cast<unsigned long long*>(ws);   // [L], then chosen [B, max_det]
+  int32_t* chosen = reinterpret_cast<int32_t*>(key + L);
+  for (int b0 = 0; b0 < B; b0 += RAGGED_CHUNK) {
+    const int n = std::min(RAGGED_CHUNK, B - b0);
+    MatchChunk ch;
+    for (int i = 0; i < RAGGED_CHUNK; ++i) ch.im[i] = images[b0 + std::min(i, n - 1)];   // unused: the last one
+    hipLaunchKernelGGL(confusion_kernel, dim3(n), dim3(MATCH_THREADS), 0, st, ch, b0, det, count, max_det, targets,
+                       label_off, L, (float)canvas_h, (float)canvas_w, conf, iou_thres, nc, matrix, key, chosen);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
 
 hipError_t launch_match(const float* det, const int32_t* count, int B, int max_det, const float* targets,
                         const int32_t* label_off, int L, const ScaleImage* images, int canvas_h, int canvas_w,

@@ -196,4 +196,31 @@ int yv7_match(const float* det, const int32_t* count, int B, int max_det, const 
   return 0;
 }
 
+size_t yv7_confusion_ws_bytes(int B, int max_det, int L) { return yv7::confusion_ws_bytes(B, max_det, L); }
+
+int yv7_confusion(const float* det, const int32_t* count, int B, int max_det, const float* targets,
+                  const int32_t* label_off, int L, const yv7_scale_desc* images, int canvas_h, int canvas_w,
+                  float conf, float iou_thres, int nc, int32_t* matrix, void* ws, size_t ws_bytes, void* stream) {
+  if (B <= 0) return fail(YV7_E_ARG, "yv7_confusion: B must be positive");
+  if (max_det <= 0) return fail(YV7_E_ARG, "yv7_confusion: max_det must be positive");
+  if (nc < 1 || nc > yv7::CONFUSION_MAX_NC) return fail(YV7_E_ARG, "yv7_confusion: nc must be in 1..1024");
+  if (L < 0) return fail(YV7_E_ARG, "yv7_confusion: L must not be negative");
+  if (L > 0 && !targets) return fail(YV7_E_ARG, "yv7_confusion: null targets with L > 0");
+  if (ws_bytes < yv7::confusion_ws_bytes(B, max_det, L)) return fail(YV7_E_ARG, "yv7_confusion: ws_bytes too small");
+  if (!det || !count || !label_off || !images || !matrix || !ws) return fail(YV7_E_ARG, "yv7_confusion: null argument");
+  if (reinterpret_cast<uintptr_t>(ws) % 8 != 0) return fail(YV7_E_ARG, "yv7_confusion: ws must be 8-byte aligned");
+  if (canvas_h <= 0 || canvas_w <= 0) return fail(YV7_E_ARG, "yv7_confusion: canvas must be positive");
+  for (int i = 0; i < B; ++i) {
+    const std::string who = "yv7_confusion: image " + std::to_string(i);
+    if (images[i].h0 <= 0 || images[i].w0 <= 0) return fail(YV7_E_ARG, who + " has a non-positive size");
+    if (!(images[i].gain > 0.f) || !std::isfinite(images[i].gain))
+      return fail(YV7_E_ARG, who + ": gain must be positive and finite");
+  }
+  hipError_t e = yv7::launch_confusion(det, count, B, max_det, targets, label_off, L,
+                                       reinterpret_cast<const yv7::ScaleImage*>(images), canvas_h, canvas_w, conf,
+                                       iou_thres, nc, matrix, ws, reinterpret_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return hip_fail(e, "yv7_confusion launch");
+  return 0;
+}
+
 }  // extern "C"

@@ -365,5 +365,10 @@ struct MatchIou {
 hipError_t launch_match(const float* det, const int32_t* count, int B, int max_det, const float* targets,
                         const int32_t* label_off, int L, const ScaleImage* images, int canvas_h, int canvas_w,
                         const MatchIou& iouv, int niou, uint8_t* correct, int32_t* claimed_by, hipStream_t st);
+constexpr int CONFUSION_MAX_NC = 1024;
+size_t confusion_ws_bytes(int B, int max_det, int L);
+hipError_t launch_confusion(const float* det, const int32_t* count, int B, int max_det, const float* targets,
+                            const int32_t* label_off, int L, const ScaleImage* images, int canvas_h, int canvas_w,
+                            float conf, float iou_thres, int nc, int32_t* matrix, void* ws, hipStream_t st);
 
 }  // namespace yv7

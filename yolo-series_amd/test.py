@@ -4,14 +4,22 @@ return value: ((mp, mr, map50, map, 0.0, 0.0, 0.0), maps, t).
 
 The reference's loop reads every batch back and matches predictions to labels per image and per class in
 Python (test.py:130-213).  Here each batch is enqueued on the stream as forward -> nms_batched(multi_label)
--> scale_boxes(ratio_pad) -> match_batch (one yv7_match launch for the whole batch) -> copies of count, det and
-correct into pinned host buffers behind an event, and the host turns a batch's buffers into statistics,
---save-txt lines and --save-json rows only after the NEXT batch has been enqueued (the last one after the loop).
-The statistics are the reference's `stats` list, so ap_per_class gives its numbers.
+-> scale_boxes(ratio_pad) -> match_batch (one yv7_match launch for the whole batch) -> with `plots`,
+ConfusionMatrix.process_batches (one yv7_confusion launch, adding into a matrix that stays on the device) -> copies
+of count, det and correct into pinned host buffers behind an event, and the host turns a batch's buffers into
+statistics, --save-txt lines and --save-json rows only after the NEXT batch has been enqueued (the last one after
+the loop).  The statistics are the reference's `stats` list, so ap_per_class gives its numbers.
 
-Not here: plots, the confusion matrix and W&B logging (`plots`, `wandb_logger`, `trace` are accepted and ignored),
-`save_hybrid` and `compute_loss` (NotImplementedError), --task study, dataset download.  Without checkpoints at
-hand `--cfg NAME --synthetic-seed S` builds seeded synthetic weights like detect.py.  There is no CPU path.
+With `plots` (the default; --task speed turns it off) the run directory receives the reference's
+confusion_matrix.png, PR_curve.png, F1_curve.png, P_curve.png and R_curve.png after the loop; the confusion matrix
+is read from the device once, there.  One deliberate deviation: called with a `model` and `save_dir` left at its
+default, test() writes no files (the reference would drop the five PNGs into the working directory); the matrix
+is still accumulated.
+
+Not here: the test_batch*_labels.jpg / _pred.jpg pictures and W&B logging (`wandb_logger`, `trace` are accepted
+and ignored), `save_hybrid` and `compute_loss` (NotImplementedError), --task study, dataset download.  Without
+checkpoints at hand `--cfg NAME --synthetic-seed S` builds seeded synthetic weights like detect.py.  There is no
+CPU path.
 
     python test.py --data data.yaml --cfg yolov7-tiny --img-size 640 --batch-size 32
 """
@@ -32,12 +40,16 @@ from models.experimental import attempt_load  # noqa: E402
 from utils.datasets import ValLoader, create_dataloader  # noqa: E402
 from utils.general import (check_dataset, check_file, check_img_size, coco80_to_coco91_class,  # noqa: E402
                            increment_path, nms_batched, scale_boxes, xyxy2xywh)
-from utils.metrics import ap_per_class, match_batch  # noqa: E402
+from utils.metrics import ConfusionMatrix, ap_per_class, match_batch  # noqa: E402
 from utils.torch_utils import select_device  # noqa: E402
 
 # what the reference reads from its global `opt` when called directly (test.py:51, 54, 90); the CLI replaces it
 opt = argparse.Namespace(device='', project='runs/test', name='exp', exist_ok=False, task='val', single_cls=False,
                          cfg=None, synthetic_seed=0)
+
+
+# test()'s default save_dir, by identity: with a model and this very object no plot files are written
+_NO_SAVE_DIR = Path('')
 
 
 class _Slot:
@@ -90,7 +102,7 @@ def test(data,
          verbose=False,
          model=None,
          dataloader=None,
-         save_dir=Path(''),
+         save_dir=_NO_SAVE_DIR,
          save_txt=False,
          save_hybrid=False,
          save_conf=False,
@@ -106,6 +118,7 @@ def test(data,
     if compute_loss is not None:
         raise NotImplementedError('compute_loss: training is not part of the MI355X inference path')
     training = model is not None
+    write_plots = bool(plots) and not (training and save_dir is _NO_SAVE_DIR)
     if training:   # called with a model (train.py's use)
         device = next(model.parameters()).device
     else:          # called directly
@@ -147,6 +160,7 @@ def test(data,
         print('Testing with YOLOv5 AP metric...')
 
     seen = 0
+    confusion_matrix = ConfusionMatrix(nc=nc) if plots else None
     names = {k: v for k, v in enumerate(model.names if hasattr(model, 'names') else model.module.names)}
     coco91class = coco80_to_coco91_class()
     s = ('%20s' + '%12s' * 6) % ('Class', 'Images', 'Labels', 'P', 'R', 'mAP@.5', 'mAP@.5:.95')
@@ -176,7 +190,10 @@ def test(data,
         # ratio_pad: gain = ratio[0] and the pads as they stand (general.py:345-346)
         descs = [(int(h0), int(w0), rp[0][0], rp[1][0], rp[1][1]) for (h0, w0), rp in shapes]
         scale_boxes(det, cnt, descs, views=False)   # native-space pred (test.py:144)
-        correct, _ = match_batch(det, cnt, t_dev, label_offsets(t_dev, nb, counts), descs, (height, width), iouv)
+        off = label_offsets(t_dev, nb, counts)
+        correct, _ = match_batch(det, cnt, t_dev, off, descs, (height, width), iouv)
+        if plots:   # test.py:188-189 for the whole batch, behind the matching launch
+            confusion_matrix.process_batches(det, cnt, t_dev, off, descs, (height, width))
         slot = slots[k % 2]
         if slot is None or not slot.fits(nb) or slot.det.shape[1] != det.shape[1]:
             slot = slots[k % 2] = _Slot(max(nb, batch_size), det.shape[1], niou)
@@ -238,7 +255,8 @@ def test(data,
     # Compute statistics (test.py:223-230)
     stats = [np.concatenate(x, 0) for x in zip(*stats)]
     if len(stats) and stats[0].any():
-        p, r, ap, f1, ap_class = ap_per_class(*stats, v5_metric=v5_metric)
+        p, r, ap, f1, ap_class = ap_per_class(*stats, plot=write_plots, v5_metric=v5_metric, save_dir=save_dir,
+                                              names=names)
         ap50, ap = ap[:, 0], ap.mean(1)   # AP@0.5, AP@0.5:0.95
         mp, mr, map50, map = p.mean(), r.mean(), ap50.mean(), ap.mean()
         nt = np.bincount(stats[3].astype(np.int64), minlength=nc)   # number of targets per class
@@ -258,6 +276,9 @@ def test(data,
     t = tuple(x / max(seen, 1) for x in (t0, t1, t0 + t1)) + (imgsz, imgsz, batch_size)
     if not training:
         print('Speed: %.1f/%.1f/%.1f ms inference/NMS/total per %gx%g image at batch-size %g' % t)
+
+    if write_plots:   # test.py:247-248; the one read of the device matrix
+        confusion_matrix.plot(save_dir=save_dir, names=list(names.values()))
 
     if save_json and len(jdict):   # test.py:256-278
         w = Path(weights[0] if isinstance(weights, list) else weights).stem if weights is not None else ''

@@ -96,6 +96,9 @@ SIGNATURES = {
     'yv7_scale_boxes': (_i, [_vp, _vp, _i, _i, ctypes.POINTER(ScaleDesc), _i, _vp, _vp, _vp, _vp]),
     'yv7_match': (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, ctypes.POINTER(ScaleDesc), _i, _i, ctypes.POINTER(_f), _i,
                        _vp, _vp, _vp]),
+    'yv7_confusion_ws_bytes': (_sz, [_i, _i, _i]),
+    'yv7_confusion': (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, ctypes.POINTER(ScaleDesc), _i, _i, _f, _f, _i, _vp, _vp,
+                           _sz, _vp]),
 }
 
 _LIB = None
