@@ -306,6 +306,56 @@ int yv7_confusion(const float* det, const int32_t* count, int B, int max_det, co
                   const int32_t* label_off, int L, const yv7_scale_desc* images, int canvas_h, int canvas_w,
                   float conf, float iou_thres, int nc, int32_t* matrix, void* ws, size_t ws_bytes, void* stream);
 
+/* Boxes and labels drawn onto the frames (replaces utils/plots.py:57-68 plot_one_box as detect.py:204-238 and
+ * Detections.display, models/common.py:953-991, call it per box on the host), for a whole batch in two launches
+ * per 64 images and without a host sync.  The drawing is integer-only and defined here, not by cv2: corners are
+ * square, edges are not anti-aliased, and the text comes from the caller's glyph atlas.
+ * images: host array, passed on by value; each frame is drawn in place.  det, count: yv7_nms's output after
+ * yv7_scale_boxes, read-only; count is clamped to [0, max_det] on the device.  palette: device uint8 [npal][3] in
+ * the frames' channel order, class c takes palette[c % npal].  names (nullable: boxes without labels): device
+ * bytes, class c's name is names[name_off[c] .. name_off[c + 1]), name_off device int32 [nc + 1]; a class >= nc
+ * gets a box and no label.  atlases: host array of n_atlas <= YV7_DRAW_MAX_ATLAS records, passed on by value.
+ * reverse: draw rows count-1 .. 0 (detect.py:209) instead of 0 .. count-1 (Detections.display).
+ * ws: device scratch of yv7_draw_ws_bytes(B, max_det) bytes, 16-byte aligned.
+ *
+ * Per row r < count[b], in draw order, later primitives over earlier ones, everything clipped to the image:
+ *   a row with a non-finite value or a negative class draws nothing.
+ *   corners: the four coordinates truncated toward zero (after a clamp to +-2^28), xa = min(x1, x2),
+ *     xb = max(x1, x2), ya, yb likewise; class = the float truncated.
+ *   outline, with t the image's thickness and lo = t / 2: the pixels with x in [xa - lo, xb - lo + t - 1] and
+ *     y in [ya - lo, yb - lo + t - 1] for which x is in [xa - lo, xa - lo + t - 1] or [xb - lo, xb - lo + t - 1],
+ *     or y is in the same bands of ya, yb; they take the class colour.
+ *   label "name d.dd": the digits are n = rint((double)conf * 100) clamped to [0, 100] (round half to even, what
+ *     f'{conf:.2f}' prints), written n / 100, '.', n / 10 % 10, n % 10.  tw = the sum of the advances,
+ *     th = cell_h.  Background: the class colour on x in [xa, xa + tw], y in [ya - th - 3, ya].  Glyph cells: rows
+ *     ya - 1 - th .. ya - 2, character k starting at xa + the advances before it; a cell pixel of coverage a is,
+ *     per channel, (a * text + (255 - a) * colour + 127) / 255 with text = (225, 255, 255).
+ * A pixel that no primitive covers is not written. */
+#define YV7_DRAW_MAX_ATLAS 8
+#define YV7_DRAW_TILE_W 64 /* the pixel kernel's tile, for tests that want shapes around it */
+#define YV7_DRAW_TILE_H 32
+
+typedef struct {
+  void* data;        /* device pointer, uint8 [h][w][3], packed rows */
+  int32_t h, w;
+  int32_t thickness; /* line thickness t >= 1 */
+  int32_t atlas;     /* which glyph atlas the image's labels use (ignored without names) */
+} yv7_draw_image;
+
+/* One text height.  metrics: device int32 [95][2], for ASCII 32 .. 126 the glyph's first column in cover and its
+ * advance width; a glyph is exactly as wide as its advance.  cover: device uint8 [cell_h][total_w] coverage.
+ * Any other byte draws as '?'. */
+typedef struct {
+  const int32_t* metrics;
+  const uint8_t* cover;
+  int32_t cell_h, total_w;
+} yv7_glyph_atlas;
+
+size_t yv7_draw_ws_bytes(int B, int max_det);
+int yv7_draw_boxes(const yv7_draw_image* images, int B, const float* det, const int32_t* count, int max_det,
+                   const uint8_t* palette, int npal, const char* names, const int32_t* name_off, int nc,
+                   const yv7_glyph_atlas* atlases, int n_atlas, int reverse, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

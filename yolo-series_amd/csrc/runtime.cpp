@@ -1,6 +1,6 @@
 // libyv7 runtime: the C ABI of include/yv7.h outside the plan — version and error reporting, NMS, the
-// End2End output mode, the letterbox (one size or ragged), the boxes' way back to image pixels and the
-// matching of predictions to labels.
+// End2End output mode, the letterbox (one size or ragged), the boxes' way back to image pixels, the
+// matching of predictions to labels and the drawing of boxes onto the frames.
 // (Plans: plan_create.cpp, plan_layout.cpp, forward.cpp.)
 #include <cmath>
 
@@ -220,6 +220,54 @@ int yv7_confusion(const float* det, const int32_t* count, int B, int max_det, co
                                        reinterpret_cast<const yv7::ScaleImage*>(images), canvas_h, canvas_w, conf,
                                        iou_thres, nc, matrix, ws, reinterpret_cast<hipStream_t>(stream));
   if (e != hipSuccess) return hip_fail(e, "yv7_confusion launch");
+  return 0;
+}
+
+static_assert(sizeof(yv7_draw_image) == sizeof(yv7::DrawImage) && sizeof(yv7_glyph_atlas) == sizeof(yv7::DrawAtlas) &&
+                  YV7_DRAW_MAX_ATLAS == yv7::DRAW_MAX_ATLAS && YV7_DRAW_TILE_W == yv7::DRAW_TILE_W &&
+                  YV7_DRAW_TILE_H == yv7::DRAW_TILE_H,
+              "the drawing kernels' records mirror the ABI descriptors");
+
+size_t yv7_draw_ws_bytes(int B, int max_det) {
+  if (B <= 0 || max_det <= 0) return 0;
+  return yv7::draw_ws_bytes(B, max_det);
+}
+
+int yv7_draw_boxes(const yv7_draw_image* images, int B, const float* det, const int32_t* count, int max_det,
+                   const uint8_t* palette, int npal, const char* names, const int32_t* name_off, int nc,
+                   const yv7_glyph_atlas* atlases, int n_atlas, int reverse, void* ws, size_t ws_bytes, void* stream) {
+  if (B <= 0) return fail(YV7_E_ARG, "yv7_draw_boxes: B must be positive");
+  if (max_det <= 0) return fail(YV7_E_ARG, "yv7_draw_boxes: max_det must be positive");
+  if (npal < 1) return fail(YV7_E_ARG, "yv7_draw_boxes: npal must be at least 1");
+  if (!images || !det || !count || !palette || !ws) return fail(YV7_E_ARG, "yv7_draw_boxes: null argument");
+  if (ws_bytes < yv7::draw_ws_bytes(B, max_det)) return fail(YV7_E_WORKSPACE, "yv7_draw_boxes: workspace too small");
+  if (reinterpret_cast<uintptr_t>(ws) % 16 != 0) return fail(YV7_E_ARG, "yv7_draw_boxes: ws must be 16-byte aligned");
+  if (names) {
+    if (!name_off || !atlases) return fail(YV7_E_ARG, "yv7_draw_boxes: names without name_off or atlases");
+    if (nc < 1) return fail(YV7_E_ARG, "yv7_draw_boxes: nc must be at least 1 with names");
+    if (n_atlas < 1 || n_atlas > YV7_DRAW_MAX_ATLAS)
+      return fail(YV7_E_ARG, "yv7_draw_boxes: n_atlas must be in 1..8 with names");
+    for (int i = 0; i < n_atlas; ++i) {
+      const std::string who = "yv7_draw_boxes: atlas " + std::to_string(i);
+      if (!atlases[i].metrics || !atlases[i].cover) return fail(YV7_E_ARG, who + " has a null pointer");
+      if (atlases[i].cell_h <= 0 || atlases[i].total_w <= 0 || atlases[i].cell_h > 4096)
+        return fail(YV7_E_SHAPE, who + " has a non-positive size or more than 4096 rows");
+    }
+  }
+  for (int i = 0; i < B; ++i) {
+    const yv7_draw_image& im = images[i];
+    const std::string who = "yv7_draw_boxes: image " + std::to_string(i);
+    if (!im.data) return fail(YV7_E_ARG, who + " has null data");
+    if (im.h <= 0 || im.w <= 0) return fail(YV7_E_SHAPE, who + " has a non-positive size");
+    if (im.h > (1 << 20) || im.w > (1 << 20)) return fail(YV7_E_SHAPE, who + " is too large (a side above 2^20)");
+    if (im.thickness < 1 || im.thickness > 4096) return fail(YV7_E_ARG, who + ": thickness must be in 1..4096");
+    if (names && (im.atlas < 0 || im.atlas >= n_atlas)) return fail(YV7_E_ARG, who + ": atlas index out of range");
+  }
+  hipError_t e = yv7::launch_draw_boxes(reinterpret_cast<const yv7::DrawImage*>(images), B, det, count, max_det,
+                                        palette, npal, reinterpret_cast<const uint8_t*>(names), name_off, nc,
+                                        reinterpret_cast<const yv7::DrawAtlas*>(atlases), n_atlas, reverse != 0, ws,
+                                        reinterpret_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return hip_fail(e, "yv7_draw_boxes launch");
   return 0;
 }
 

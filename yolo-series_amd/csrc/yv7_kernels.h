@@ -370,5 +370,21 @@ size_t confusion_ws_bytes(int B, int max_det, int L);
 hipError_t launch_confusion(const float* det, const int32_t* count, int B, int max_det, const float* targets,
                             const int32_t* label_off, int L, const ScaleImage* images, int canvas_h, int canvas_w,
                             float conf, float iou_thres, int nc, int32_t* matrix, void* ws, hipStream_t st);
+// draw.hip: DrawImage and DrawAtlas have the layouts of yv7_draw_image / yv7_glyph_atlas; the atlases travel by
+// value as well
+constexpr int DRAW_TILE_W = 64, DRAW_TILE_H = 32, DRAW_MAX_ATLAS = 8;
+struct DrawImage {
+  uint8_t* data;
+  int32_t h, w, t, atlas;
+};
+struct DrawAtlas {
+  const int32_t* metrics;
+  const uint8_t* cover;
+  int32_t cell_h, total_w;
+};
+size_t draw_ws_bytes(int B, int max_det);
+hipError_t launch_draw_boxes(const DrawImage* images, int B, const float* det, const int32_t* count, int max_det,
+                             const uint8_t* palette, int npal, const uint8_t* names, const int32_t* name_off, int nc,
+                             const DrawAtlas* atlases, int n_atlas, int reverse, void* ws, hipStream_t st);
 
 }  // namespace yv7

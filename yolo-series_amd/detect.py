@@ -4,8 +4,9 @@ on the MI355X path: attempt_load -> LoadImages (GPU letterbox) -> model(img)[0] 
 
 Differences, all forced by the environment: frames are decoded by PIL (cv2 is absent; decode parity
 unpinned), there are no checkpoints offline so `--cfg NAME --synthetic-seed S` builds seeded synthetic
-weights instead of `--weights`, and drawing/saving annotated images (utils/plots.py, cv2) is out of
-scope — `--save-txt` writes the reference's label format.  There is no CPU execution path.
+weights instead of `--weights`, and annotated images (detect.py:204-238) are opt-in: `--save-img` draws the
+boxes on the device (utils/plots.py plot_boxes, one yv7_draw_boxes call per group of files) and saves them with
+PIL; `--save-txt` writes the reference's label format.  There is no CPU execution path.
 
 `--batch-size N` (N > 1) runs groups of up to N files, of whatever sizes, per forward: one ragged letterbox
 launch (yv7_letterbox_ragged), one forward, one batched NMS, one box-scaling launch (yv7_scale_boxes with the
@@ -23,6 +24,7 @@ from pathlib import Path
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from models.experimental import attempt_load  # noqa: E402
@@ -30,7 +32,24 @@ from utils.datasets import (OUT_F16_CHW, OUT_F32_CHW, LoadImages, imread, letter
                             letterbox_ragged)
 from utils.general import (check_img_size, nms_batched, non_max_suppression, scale_boxes, scale_coords,  # noqa: E402
                            scale_desc, xyxy2xywh)
+from utils.plots import color_list, plot_boxes  # noqa: E402
 from utils.torch_utils import select_device, time_synchronized  # noqa: E402
+
+
+def bgr_colors():
+    """color_list() in the frames' channel order: they are BGR until they are saved."""
+    return [c[::-1] for c in color_list()]
+
+
+def save_images(frames, paths, save_dir):
+    """Annotated BGR frames on the device -> save_dir / name, RGB, with PIL: one download for the group."""
+    from PIL import Image
+    flat = torch.cat([f.reshape(-1) for f in frames]).cpu().numpy()
+    off = 0
+    for f, path in zip(frames, paths):
+        im = flat[off:off + f.numel()].reshape(tuple(f.shape))
+        off += f.numel()
+        Image.fromarray(im[:, :, ::-1]).save(save_dir / Path(path).name)
 
 
 def load_model(opt, device):
@@ -52,6 +71,10 @@ def detect_batched(opt, model, dataset, imgsz, half, names, save_dir):
         paths = files[g0:g0 + opt.batch_size]
         im0s = [imread(p) for p in paths]                  # BGR, sizes may differ
         geoms = [letterbox_geometry(im0.shape[:2], (imgsz, imgsz), auto=False) for im0 in im0s]   # datasets.py:196
+        if opt.save_img:   # one upload: the letterbox and the drawing take the same tensors
+            packed = torch.from_numpy(np.concatenate([im0.reshape(-1) for im0 in im0s])).to(device)
+            sizes = [im0.size for im0 in im0s]
+            im0s = [p.view(im0.shape) for p, im0 in zip(packed.split(sizes), im0s)]
         t1 = time_synchronized()
         img = letterbox_ragged(im0s, geoms, (imgsz, imgsz), swap_rb=True, device=device,
                                out_kind=OUT_F16_CHW if half else OUT_F32_CHW)
@@ -62,6 +85,9 @@ def detect_batched(opt, model, dataset, imgsz, half, names, save_dir):
         scale_boxes(det, cnt, [scale_desc(img.shape[2:], im0.shape) for im0 in im0s], round_boxes=True, views=False)
         counts = cnt.tolist()
         t3 = time_synchronized()
+        if opt.save_img:   # detect.py:216-218: name + conf, thickness 1, the last row first
+            save_images(plot_boxes(im0s, det, cnt, names=names, colors=bgr_colors(), line_thickness=1, reverse=True),
+                        paths, save_dir)
         for i, (path, im0) in enumerate(zip(paths, im0s)):
             d, s = det[i, :counts[i]].cpu(), ''
             gn = torch.tensor(im0.shape)[[1, 0, 1, 0]]      # normalization gain whwh
@@ -98,6 +124,8 @@ def detect(opt):
     save_dir = Path(opt.project) / opt.name
     if opt.save_txt:
         (save_dir / 'labels').mkdir(parents=True, exist_ok=True)
+    if opt.save_img:
+        save_dir.mkdir(parents=True, exist_ok=True)
     results = []
     t0 = time.time()
     if opt.batch_size > 1:
@@ -131,6 +159,11 @@ def detect(opt):
                             xywh = (xyxy2xywh(torch.tensor(xyxy).view(1, 4)) / gn).view(-1).tolist()
                             line = (cls, *xywh, conf) if opt.save_conf else (cls, *xywh)
                             f.write(('%g ' * len(line)).rstrip() % line + '\n')
+            if opt.save_img:   # detect.py:216-218 through the batch's drawing path, a batch of one
+                cnt = torch.tensor([len(det)], dtype=torch.int32, device=device)
+                box = det[None].float().contiguous() if len(det) else torch.zeros((1, 1, 6), device=device)
+                save_images(plot_boxes([im0], box, cnt, names=names, colors=bgr_colors(), line_thickness=1,
+                                       reverse=True), [path], save_dir)
             if not opt.quiet:
                 print(f'{s}Done. ({(1E3 * (t2 - t1)):.1f}ms) Inference, ({(1E3 * (t3 - t2)):.1f}ms) NMS')
             results.append((path, det.cpu()))
@@ -152,6 +185,7 @@ def parse_opt(argv=None):
     ap.add_argument('--device', default='', help='cuda device, i.e. 0 or 0,1,2,3')
     ap.add_argument('--save-txt', action='store_true', help='save results to *.txt')
     ap.add_argument('--save-conf', action='store_true', help='save confidences in --save-txt labels')
+    ap.add_argument('--save-img', action='store_true', help='save the images with boxes and labels drawn')
     ap.add_argument('--classes', nargs='+', type=int, help='filter by class: --class 0, or --class 0 2 3')
     ap.add_argument('--agnostic-nms', action='store_true', help='class-agnostic NMS')
     ap.add_argument('--augment', action='store_true', help='augmented inference')

@@ -10,8 +10,8 @@ layer and never on the CPU, so calling a layer directly raises.
 The model's front door for real images is here too (common.py:852-1012): NMS, autoShape ("a list of images
 of whatever size in, boxes in each image's own pixels out") and its result class Detections.  autoShape runs one
 ragged letterbox launch, one forward, one batched NMS and one box-scaling launch per call (libyv7
-yv7_letterbox_ragged / yv7_nms / yv7_scale_boxes); drawing (show / save / render, utils/plots.py) and URL
-inputs are out of scope.
+yv7_letterbox_ragged / yv7_nms / yv7_scale_boxes), and Detections.render / save / show draw the boxes on the
+device in one more call (yv7_draw_boxes, utils/plots.py).  URL inputs are out of scope.
 
 Folding (Model.fuse in the reference) is restated here with the reference arithmetic:
   Conv:    fuse_conv_and_bn      utils/torch_utils.py:181-201
@@ -27,7 +27,8 @@ import torch
 import torch.nn as nn
 
 from utils.datasets import OUT_F16_CHW, OUT_F32_CHW, autoshape_geometry, letterbox_ragged
-from utils.general import nms_batched, non_max_suppression, scale_boxes, xyxy2xywh
+from utils.general import increment_path, nms_batched, non_max_suppression, scale_boxes, xyxy2xywh
+from utils.plots import color_list, plot_boxes
 from utils.torch_utils import fuse_conv_and_bn, time_synchronized
 
 
@@ -294,15 +295,16 @@ class autoShape(nn.Module):  # common.py:865-932
         counts = cnt.tolist()   # the one host sync: variable-length outputs
         pred, xywh, xyxyn, xywhn = ([v[i, :c] for i, c in enumerate(counts)] for v in (det, *views))
         t.append(time_synchronized())
-        return Detections(imgs, pred, files, t, self.names, x.shape, views=(xywh, xyxyn, xywhn))
+        return Detections(imgs, pred, files, t, self.names, x.shape, views=(xywh, xyxyn, xywhn), batch=(det, cnt))
 
 
 class Detections:  # common.py:935-1012
     """Results of one autoShape call: per image pred = xyxy [n, 6] (x1, y1, x2, y2, conf, cls) in the image's own
     pixels, and the views xywh (centre, size), xyxyn, xywhn (normalised by the image's w, h)."""
 
-    def __init__(self, imgs, pred, files, times=None, names=None, shape=None, views=None):
+    def __init__(self, imgs, pred, files, times=None, names=None, shape=None, views=None, batch=None):
         self.imgs = imgs      # list of images as given (numpy arrays or HIP tensors, HWC)
+        self._batch = batch   # autoShape's (det [B, max_det, 6], count [B]) that pred's rows are views of
         self.pred = pred      # list of tensors pred[0] = (xyxy, conf, cls)
         self.names = names    # class names
         self.files = files    # image filenames
@@ -331,14 +333,49 @@ class Detections:  # common.py:935-1012
             print(self._summary(i))
         print(f'Speed: %.1fms pre-process, %.1fms inference, %.1fms NMS per image at shape {tuple(self.s)}' % self.t)
 
+    def _draw(self, what):
+        """The boxes of every image drawn by one plot_boxes call (Detections.display's plot_one_box loop,
+        common.py:965-968: forward order, 'name conf' labels, color_list(), the per-image line thickness)."""
+        if any(not (isinstance(p, torch.Tensor) and p.is_cuda) for p in self.pred):
+            raise NotImplementedError(f'Detections.{what}: drawing runs on the ROCm device (libyv7 yv7_draw_boxes); '
+                                      f'these predictions are CPU tensors and there is no CPU drawing path')
+        if self.n == 0:
+            return
+        if self._batch is not None:
+            det, cnt = self._batch
+        else:   # results assembled by hand: the fixed-shape form the kernel reads
+            dev = self.pred[0].device
+            cnt = torch.tensor([len(p) for p in self.pred], dtype=torch.int32, device=dev)
+            det = torch.zeros((self.n, max(int(cnt.max()), 1), 6), dtype=torch.float32, device=dev)
+            for i, p in enumerate(self.pred):
+                det[i, :len(p)] = p
+        out = plot_boxes(self.imgs, det, cnt, names=self.names, colors=color_list(), reverse=False)
+        host = [i for i, im in enumerate(self.imgs) if isinstance(im, np.ndarray)]
+        if host:   # one download for the batch
+            flat = torch.cat([out[i].reshape(-1) for i in host]).cpu().numpy()
+            off = 0
+            for i in host:
+                shape = self.imgs[i].shape
+                self.imgs[i] = flat[off:off + out[i].numel()].reshape(shape)
+                off += out[i].numel()
+
     def show(self):
-        raise NotImplementedError('Detections.show: drawing (utils/plots.py) is not part of this package')
+        from PIL import Image
+        for im, f in zip(self.render(), self.files):
+            Image.fromarray(im.cpu().numpy() if isinstance(im, torch.Tensor) else im).show(f)
 
     def save(self, save_dir='runs/hub/exp'):
-        raise NotImplementedError('Detections.save: drawing (utils/plots.py) is not part of this package')
+        from PIL import Image
+        imgs = self.render()   # raises for CPU predictions before anything is written
+        save_dir = increment_path(save_dir, exist_ok=save_dir != 'runs/hub/exp')   # common.py:984-987
+        Path(save_dir).mkdir(parents=True, exist_ok=True)
+        for i, (im, f) in enumerate(zip(imgs, self.files)):
+            Image.fromarray(im.cpu().numpy() if isinstance(im, torch.Tensor) else im).save(Path(save_dir) / f)
+            print(f"{'Saved' * (i == 0)} {f}", end=',' if i < self.n - 1 else f' to {save_dir}\n')
 
     def render(self):
-        raise NotImplementedError('Detections.render: drawing (utils/plots.py) is not part of this package')
+        self._draw('render')
+        return self.imgs
 
     def pandas(self):
         """A copy whose four views are pandas DataFrames, i.e. print(results.pandas().xyxy[0])."""

@@ -1,0 +1,195 @@
+"""Boxes and labels drawn on the device — the reference's utils/plots.py:29-34, 57-68.
+
+`plot_boxes(frames, det, count, ...)` is plot_one_box for a whole batch: one yv7_draw_boxes call (libyv7, two
+launches per 64 images) on nms_batched's fixed-shape output after scale_boxes, stream-ordered, with no host read.
+The drawing is defined by the contract in include/yv7.h, not by cv2 (absent here): square corners, no anti-aliased
+edges, and the text comes from PIL's default font rendered once into a glyph atlas.  There is no CPU path and no
+plot_one_box for one box on a host array.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+import torch
+
+from utils.datasets import _hip_device, pack_frames
+from yv7 import _lib as L
+
+
+def color_list():   # plots.py:29-34: the first ten matplotlib colours as (r, g, b)
+    import matplotlib.colors
+
+    def hex2rgb(h):
+        return tuple(int(h[1 + i:1 + i + 2], 16) for i in (0, 2, 4))
+
+    return [hex2rgb(h) for h in matplotlib.colors.TABLEAU_COLORS.values()]
+
+
+def line_thickness(shape):   # plots.py:59: line / font thickness of an image of shape (h, w, ...)
+    return round(0.002 * (shape[0] + shape[1]) / 2) + 1
+
+
+_line_thickness = line_thickness   # plot_boxes has a parameter of that name
+
+
+def text_height(t):
+    """The glyph cell's height for line thickness t.  The reference draws cv2's 22-pixel face at fontScale t / 3;
+    22 pixels is that face's height above the baseline, and the cell here also holds the descenders, which in PIL's
+    default font of size 22 makes 28 rows.  10 rows (size 8) is the smallest that still reads."""
+    return max(round(28 * t / 3), 10)
+
+
+_ATLAS_HOST, _ATLAS_DEV, _NAMES, _PALETTE = {}, {}, {}, {}
+
+
+def _font(cell_h):
+    """PIL's default font at the largest size whose ascent + descent fits cell_h rows; without FreeType, PIL's
+    built-in bitmap font, whatever cell_h."""
+    from PIL import ImageFont
+    try:
+        for size in range(cell_h, 0, -1):
+            f = ImageFont.load_default(size)
+            if sum(f.getmetrics()) <= cell_h or size == 1:
+                return f
+    except (OSError, TypeError, AttributeError):
+        pass
+    return ImageFont.load_default()
+
+
+def glyph_atlas_host(cell_h):
+    """(metrics int32 [95, 2], cover uint8 [cell_h, total_w]) for ASCII 32 .. 126: each glyph's first column and
+    advance, and its coverage.  Every glyph is rendered on its own and clipped to its advance."""
+    cell_h = int(cell_h)
+    if cell_h not in _ATLAS_HOST:
+        from PIL import Image, ImageDraw, ImageFont
+        font = _font(cell_h)
+        scalable = isinstance(font, ImageFont.FreeTypeFont)
+        cells = []
+        for c in range(32, 127):
+            ch = chr(c)
+            adv = max(int(math.ceil(font.getlength(ch))), 1)
+            rows = cell_h if scalable else max(font.getbbox(ch)[3], 1)
+            im = Image.new('L', (adv, rows), 0)
+            ImageDraw.Draw(im).text((0, 0), ch, fill=255, font=font)
+            cells.append(np.asarray(im, dtype=np.uint8))
+        rows = max(c.shape[0] for c in cells)   # the bitmap font: its own height
+        cells = [np.pad(c, ((0, rows - c.shape[0]), (0, 0))) for c in cells]
+        adv = np.array([c.shape[1] for c in cells], np.int32)
+        col = np.concatenate([[0], np.cumsum(adv)[:-1]]).astype(np.int32)
+        _ATLAS_HOST[cell_h] = np.stack([col, adv], 1).astype(np.int32), np.ascontiguousarray(np.concatenate(cells, 1))
+    return _ATLAS_HOST[cell_h]
+
+
+class Atlas:
+    """A glyph atlas on the device: metrics int32 [95, 2] (column, advance) and cover uint8 [cell_h, total_w]."""
+
+    def __init__(self, metrics, cover, device):
+        metrics, cover = np.ascontiguousarray(metrics, np.int32), np.ascontiguousarray(cover, np.uint8)
+        if metrics.shape != (95, 2) or cover.ndim != 2:
+            raise ValueError(f'glyph atlas: expected metrics [95, 2] and cover [cell_h, total_w], got '
+                             f'{metrics.shape} and {cover.shape}')
+        if int(metrics[:, 1].sum()) != cover.shape[1]:
+            raise ValueError('glyph atlas: the advances must sum to the coverage map\'s width')
+        self.cell_h, self.total_w = (int(v) for v in cover.shape)
+        self.metrics, self.cover = torch.from_numpy(metrics).to(device), torch.from_numpy(cover).to(device)
+
+
+def glyph_atlas(cell_h, device=None):
+    """The atlas of PIL's default font for a cell of cell_h rows, cached per (cell_h, device)."""
+    device = _hip_device(device if device is not None else 'cuda')
+    key = int(cell_h), device
+    if key not in _ATLAS_DEV:
+        _ATLAS_DEV[key] = Atlas(*glyph_atlas_host(int(cell_h)), device)
+    return _ATLAS_DEV[key]
+
+
+def _names_blob(names, device):
+    key = tuple(names), device
+    if key not in _NAMES:
+        raw = [n if isinstance(n, bytes) else str(n).encode('utf-8') for n in names]
+        off = np.concatenate([[0], np.cumsum([len(r) for r in raw])]).astype(np.int32)
+        blob = np.frombuffer(b''.join(raw) + b'\0', np.uint8).copy()   # never empty
+        _NAMES[key] = torch.from_numpy(blob).to(device), torch.from_numpy(off).to(device), len(raw)
+    return _NAMES[key]
+
+
+def _palette(colors, device):
+    key = tuple(tuple(int(v) for v in c) for c in colors), device
+    if key not in _PALETTE:
+        pal = np.array(key[0], np.uint8).reshape(-1, 3)
+        _PALETTE[key] = torch.from_numpy(pal).to(device)
+    return _PALETTE[key]
+
+
+def plot_boxes(frames, det, count, names=None, colors=None, line_thickness=None, reverse=False, atlas=None):
+    """plot_one_box (plots.py:57-68) for every row < count[b] of every frame, in one yv7_draw_boxes call.
+
+    frames: uint8 HWC numpy arrays (uploaded in one packed copy, left unmodified) or contiguous HIP tensors (drawn
+    in place), any sizes.  det [B, max_det, 6] fp32 and count [B] int32 on the device, as nms_batched returns them
+    after scale_boxes.  names: class names for 'name conf' labels, None for boxes alone.  colors: (c0, c1, c2)
+    tuples in the frames' channel order, default color_list().  line_thickness: one value or one per frame, default
+    the reference's rule per frame.  reverse: draw the last row first (detect.py:209).  atlas: an Atlas to use for
+    every frame instead of glyph_atlas(text_height(t)).
+    Returns the annotated frames as a list of HIP tensors, stream-ordered: nothing is read back."""
+    if not (isinstance(det, torch.Tensor) and det.is_cuda):
+        raise RuntimeError('plot_boxes draws on a ROCm device (libyv7); got CPU detections')
+    device = det.device
+    B = len(frames)
+    if det.dtype != torch.float32 or det.dim() != 3 or det.shape[0] != B or det.shape[2] != 6 or \
+            not det.is_contiguous() or B == 0:
+        raise ValueError(f'plot_boxes: expected contiguous fp32 det [B, max_det, 6] for {B} frames')
+    if count.dtype != torch.int32 or tuple(count.shape) != (B,) or not count.is_contiguous() or count.device != device:
+        raise ValueError('plot_boxes: count must be int32 [B] on det\'s device')
+    for f in frames:
+        is_t = isinstance(f, torch.Tensor)
+        if f.dtype != (torch.uint8 if is_t else np.uint8) or f.ndim != 3 or f.shape[2] != 3:
+            raise ValueError(f'plot_boxes: expected uint8 [H, W, 3] frames, got {f.dtype} {tuple(f.shape)}')
+        if is_t and not f.is_contiguous():
+            raise ValueError('plot_boxes: a tensor frame is drawn in place and must be contiguous')
+    max_det = det.shape[1]
+    ptrs, keep = pack_frames(frames, device)
+    out, packed = [], keep[0] if any(isinstance(f, np.ndarray) for f in frames) else None
+    for f, p in zip(frames, ptrs):
+        if isinstance(f, torch.Tensor):
+            out.append(f)
+        else:
+            o = p - packed.data_ptr()
+            out.append(packed[o:o + f.size].view(f.shape))
+    if line_thickness is None:
+        ts = [_line_thickness(f.shape) for f in frames]
+    else:
+        ts = list(line_thickness) if isinstance(line_thickness, (list, tuple)) else [line_thickness] * B
+    ts = [int(t) for t in ts]
+    if len(ts) != B or min(ts) < 1:
+        raise ValueError('plot_boxes: line_thickness must be at least 1, one value or one per frame')
+
+    pal = _palette(colors if colors is not None else color_list(), device)
+    atlases, which = [], [0] * B
+    if names is not None:
+        if atlas is not None:
+            atlases = [atlas]
+        else:
+            heights = sorted({text_height(t) for t in ts})
+            if len(heights) > L.DRAW_MAX_ATLAS:
+                raise ValueError(f'plot_boxes: more than {L.DRAW_MAX_ATLAS} text heights in one batch')
+            atlases = [glyph_atlas(h, device) for h in heights]
+            which = [heights.index(text_height(t)) for t in ts]
+        blob, off, nc = _names_blob(names, device)
+    images = (L.DrawImage * B)()
+    for d, p, f, t, a in zip(images, ptrs, frames, ts, which):
+        d.data, d.h, d.w, d.thickness, d.atlas = p, f.shape[0], f.shape[1], t, a
+    arr = (L.GlyphAtlas * max(len(atlases), 1))()
+    for d, a in zip(arr, atlases):
+        d.metrics, d.cover, d.cell_h, d.total_w = a.metrics.data_ptr(), a.cover.data_ptr(), a.cell_h, a.total_w
+    lib = L.lib()
+    ws = torch.empty(int(lib.yv7_draw_ws_bytes(B, max_det)), dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        stream = torch.cuda.current_stream(device).cuda_stream
+        rc = lib.yv7_draw_boxes(images, B, det.data_ptr(), count.data_ptr(), max_det, pal.data_ptr(), pal.shape[0],
+                                blob.data_ptr() if names is not None else None,
+                                off.data_ptr() if names is not None else None, nc if names is not None else 0,
+                                arr if atlases else None, len(atlases), int(bool(reverse)), ws.data_ptr(),
+                                ws.numel(), stream)
+    L.check(rc, 'yv7_draw_boxes')
+    return out

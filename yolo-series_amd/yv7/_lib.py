@@ -67,6 +67,20 @@ class ScaleDesc(ctypes.Structure):
                 ('pad_w', ctypes.c_float), ('pad_h', ctypes.c_float)]
 
 
+class DrawImage(ctypes.Structure):
+    """yv7_draw_image: one frame to draw on."""
+    _fields_ = [('data', ctypes.c_void_p), ('h', ctypes.c_int32), ('w', ctypes.c_int32),
+                ('thickness', ctypes.c_int32), ('atlas', ctypes.c_int32)]
+
+
+class GlyphAtlas(ctypes.Structure):
+    """yv7_glyph_atlas: the glyphs of one text height."""
+    _fields_ = [('metrics', ctypes.c_void_p), ('cover', ctypes.c_void_p), ('cell_h', ctypes.c_int32),
+                ('total_w', ctypes.c_int32)]
+
+
+DRAW_MAX_ATLAS, DRAW_TILE_W, DRAW_TILE_H = 8, 64, 32
+
 _vp, _i, _i64, _sz, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float
 
 # name -> (restype, argtypes); every symbol include/yv7.h declares
@@ -99,6 +113,9 @@ SIGNATURES = {
     'yv7_confusion_ws_bytes': (_sz, [_i, _i, _i]),
     'yv7_confusion': (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, ctypes.POINTER(ScaleDesc), _i, _i, _f, _f, _i, _vp, _vp,
                            _sz, _vp]),
+    'yv7_draw_ws_bytes': (_sz, [_i, _i]),
+    'yv7_draw_boxes': (_i, [ctypes.POINTER(DrawImage), _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i,
+                            ctypes.POINTER(GlyphAtlas), _i, _i, _vp, _sz, _vp]),
 }
 
 _LIB = None
