@@ -29,6 +29,8 @@
  *                     predictions to labels for mAP
  *   yv7_confusion     ConfusionMatrix.process_batch over a      utils/metrics.py:121-159 as called from
  *                     batch, into a matrix kept on the device   test.py:137-140,181-189
+ *   yv7_coco_match    pycocotools' COCOeval.evaluateImg (bbox)  test.py:256-278: ev.evaluate() of the
+ *                     over a batch, on the JSON rows' values    third-party library the reference calls
  */
 #ifndef YV7_H
 #define YV7_H
@@ -305,6 +307,45 @@ size_t yv7_confusion_ws_bytes(int B, int max_det, int L);
 int yv7_confusion(const float* det, const int32_t* count, int B, int max_det, const float* targets,
                   const int32_t* label_off, int L, const yv7_scale_desc* images, int canvas_h, int canvas_w,
                   float conf, float iou_thres, int nc, int32_t* matrix, void* ws, size_t ws_bytes, void* stream);
+
+/* COCO bbox matching (restates pycocotools' COCOeval.evaluateImg, which test.py:256-278 reaches through
+ * ev.evaluate(); the library itself is not used), for a whole batch in one launch per 64 images and without a host
+ * sync.  All inputs are read-only; count and gt_off are clamped on the device.  All arithmetic is IEEE double
+ * without contraction unless said otherwise; the integer outputs are identical from run to run.
+ * det, count: yv7_nms's output after yv7_scale_boxes (native pixels), B images of max_det rows.
+ * gts: device [G,7] double rows (class index, x, y, w, h, area, iscrowd) sorted by image, in annotation order
+ * within an image; gt_off: device [B+1], image b's gts are rows gt_off[b] .. gt_off[b+1].  A gt belongs to the
+ * class of a row r iff (double)det[r,5] == gts[g,0].
+ * Values: the evaluation runs on what the predictions JSON holds.  In fp32, in xyxy2xywh's order, w = x2 - x1,
+ * h = y2 - y1, x = (x1 + x2) / 2 - w / 2, y = (y1 + y2) / 2 - h / 2; each becomes rint((double)v * 1000.0) / 1000.0
+ * and the score rint((double)s * 100000.0) / 100000.0 (the products are exact, so this is Python's round(v, 3) and
+ * round(s, 5)).  A detection's area is w * h of the rounded values; a gt's area is its own field and is used
+ * only for the area ranges.
+ * IoU(d, g): w = min(d.x + d.w, g.x + g.w) - max(d.x, g.x), h likewise; 0 if w <= 0 or h <= 0; else i = w * h and
+ * i / (d.w * d.h) for a crowd gt, i / (d.w * d.h + g.w * g.h - i) otherwise.
+ * Per image and class: the rows r < count[b] of the class in (rounded score descending, row ascending) order;
+ * a row's position is its rank, and rows at position >= 100 take no part.  For each of the area ranges
+ * a = [0, 1e10], [0, 1024], [1024, 9216], [9216, 1e10] a gt is ignored iff it is a crowd or its area lies outside
+ * the range (area < lo or area > hi), and the gts are ordered not-ignored first, annotation order within each
+ * group.  For each threshold t of np.linspace(0.5, 0.95, 10) and each detection in rank order:
+ *     iou = min(t, 1 - 1e-10); m = -1
+ *     for g in gts: if matched[g] and not crowd[g]: continue
+ *                   if m > -1 and not ignored[m] and ignored[g]: break
+ *                   if IoU(d, g) < iou: continue
+ *                   iou = IoU(d, g); m = g
+ *     if m > -1: the detection is matched, ignored iff ignored[m]; matched[m] = 1
+ * so that among equal IoUs the last gt wins and an IoU equal to the threshold matches.  An unmatched detection is
+ * ignored iff its own area lies outside the range.
+ * rank [B,max_det] int32: the position within (image, class), -1 for rows >= count[b] or at position >= 100.
+ * flags [B,max_det,4] uint32, one word per area range: bit t = matched at threshold t, bit 10 + t = ignored at
+ * threshold t; 0 where rank is -1.  Both are written in full.
+ * ws: device scratch of at least yv7_coco_match_ws_bytes(B, max_det, G) bytes, 8-byte aligned (the sorted rows and
+ * the per-gt match state: neither max_det, nor the rows per class, nor the gts per image or class are limited).
+ * A NaN score or class gives that image meaningless flags; nothing is read or written out of bounds. */
+size_t yv7_coco_match_ws_bytes(int B, int max_det, int G);
+int yv7_coco_match(const float* det, const int32_t* count, int B, int max_det, const double* gts,
+                   const int32_t* gt_off, int G, uint32_t* flags, int32_t* rank, void* ws, size_t ws_bytes,
+                   void* stream);
 
 /* Boxes and labels drawn onto the frames (replaces utils/plots.py:57-68 plot_one_box as detect.py:204-238 and
  * Detections.display, models/common.py:953-991, call it per box on the host), for a whole batch in two launches

@@ -223,6 +223,25 @@ int yv7_confusion(const float* det, const int32_t* count, int B, int max_det, co
   return 0;
 }
 
+size_t yv7_coco_match_ws_bytes(int B, int max_det, int G) { return yv7::coco_match_ws_bytes(B, max_det, G); }
+
+int yv7_coco_match(const float* det, const int32_t* count, int B, int max_det, const double* gts,
+                   const int32_t* gt_off, int G, uint32_t* flags, int32_t* rank, void* ws, size_t ws_bytes,
+                   void* stream) {
+  if (B <= 0) return fail(YV7_E_ARG, "yv7_coco_match: B must be positive");
+  if (max_det <= 0) return fail(YV7_E_ARG, "yv7_coco_match: max_det must be positive");
+  if (G < 0) return fail(YV7_E_ARG, "yv7_coco_match: G must not be negative");
+  if (G > 0 && !gts) return fail(YV7_E_ARG, "yv7_coco_match: null gts with G > 0");
+  if (ws_bytes < yv7::coco_match_ws_bytes(B, max_det, G))
+    return fail(YV7_E_WORKSPACE, "yv7_coco_match: ws_bytes too small");
+  if (!det || !count || !gt_off || !flags || !rank || !ws) return fail(YV7_E_ARG, "yv7_coco_match: null argument");
+  if (reinterpret_cast<uintptr_t>(ws) % 8 != 0) return fail(YV7_E_ARG, "yv7_coco_match: ws must be 8-byte aligned");
+  hipError_t e = yv7::launch_coco_match(det, count, B, max_det, gts, gt_off, G, flags, rank, ws,
+                                        reinterpret_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return hip_fail(e, "yv7_coco_match launch");
+  return 0;
+}
+
 static_assert(sizeof(yv7_draw_image) == sizeof(yv7::DrawImage) && sizeof(yv7_glyph_atlas) == sizeof(yv7::DrawAtlas) &&
                   YV7_DRAW_MAX_ATLAS == yv7::DRAW_MAX_ATLAS && YV7_DRAW_TILE_W == yv7::DRAW_TILE_W &&
                   YV7_DRAW_TILE_H == yv7::DRAW_TILE_H,

@@ -370,6 +370,9 @@ size_t confusion_ws_bytes(int B, int max_det, int L);
 hipError_t launch_confusion(const float* det, const int32_t* count, int B, int max_det, const float* targets,
                             const int32_t* label_off, int L, const ScaleImage* images, int canvas_h, int canvas_w,
                             float conf, float iou_thres, int nc, int32_t* matrix, void* ws, hipStream_t st);
+size_t coco_match_ws_bytes(int B, int max_det, int G);
+hipError_t launch_coco_match(const float* det, const int32_t* count, int B, int max_det, const double* gts,
+                             const int32_t* gt_off, int G, uint32_t* flags, int32_t* rank, void* ws, hipStream_t st);
 // draw.hip: DrawImage and DrawAtlas have the layouts of yv7_draw_image / yv7_glyph_atlas; the atlases travel by
 // value as well
 constexpr int DRAW_TILE_W = 64, DRAW_TILE_H = 32, DRAW_MAX_ATLAS = 8;

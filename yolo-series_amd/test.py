@@ -10,6 +10,12 @@ of count, det and correct into pinned host buffers behind an event, and the host
 statistics, --save-txt lines and --save-json rows only after the NEXT batch has been enqueued (the last one after
 the loop).  The statistics are the reference's `stats` list, so ap_per_class gives its numbers.
 
+With `save_json` and the annotation file (`opt.anno_json` / --anno-json) at hand the reference's COCO numbers
+(test.py:256-278) replace `map` and `map50`.  Where pycocotools can be imported it runs exactly as in the
+reference.  Where it cannot, its bbox COCOeval is restated here (utils/cocoeval.py): each batch gains one
+yv7_coco_match launch behind the matching, whose flag words travel in the same pinned slot, and the host folds them
+into the 12-line summary after the loop.
+
 With `plots` (the default; --task speed turns it off) the run directory receives the reference's
 confusion_matrix.png, PR_curve.png, F1_curve.png, P_curve.png and R_curve.png after the loop; the confusion matrix
 is read from the device once, there.  One deliberate deviation: called with a `model` and `save_dir` left at its
@@ -17,7 +23,8 @@ default, test() writes no files (the reference would drop the five PNGs into the
 is still accumulated.
 
 Not here: the test_batch*_labels.jpg / _pred.jpg pictures and W&B logging (`wandb_logger`, `trace` are accepted
-and ignored), `save_hybrid` and `compute_loss` (NotImplementedError), --task study, dataset download.  Without
+and ignored), `save_hybrid` and `compute_loss` (NotImplementedError), --task study, dataset download, COCO
+segmentation and keypoint evaluation (the restated COCOeval is the bbox one).  Without
 checkpoints at hand `--cfg NAME --synthetic-seed S` builds seeded synthetic weights like detect.py.  There is no
 CPU path.
 
@@ -45,7 +52,7 @@ from utils.torch_utils import select_device  # noqa: E402
 
 # what the reference reads from its global `opt` when called directly (test.py:51, 54, 90); the CLI replaces it
 opt = argparse.Namespace(device='', project='runs/test', name='exp', exist_ok=False, task='val', single_cls=False,
-                         cfg=None, synthetic_seed=0)
+                         cfg=None, synthetic_seed=0, anno_json='./coco/annotations/instances_val2017.json')
 
 
 # test()'s default save_dir, by identity: with a model and this very object no plot files are written
@@ -55,10 +62,12 @@ _NO_SAVE_DIR = Path('')
 class _Slot:
     """Pinned host buffers for one batch in flight, and the event behind which they are valid."""
 
-    def __init__(self, nb, max_det, niou):
+    def __init__(self, nb, max_det, niou, coco=False):
         self.count = torch.empty((nb,), dtype=torch.int32, pin_memory=True)
         self.det = torch.empty((nb, max_det, 6), dtype=torch.float32, pin_memory=True)
         self.correct = torch.empty((nb, max_det, niou), dtype=torch.uint8, pin_memory=True)
+        self.flags = torch.empty((nb, max_det, 4), dtype=torch.int32, pin_memory=True) if coco else None
+        self.rank = torch.empty((nb, max_det), dtype=torch.int32, pin_memory=True) if coco else None
         self.event = torch.cuda.Event()
         self.targets = self.paths = self.shapes = None
 
@@ -168,6 +177,21 @@ def test(data,
     jdict, stats, timers = [], [], []
     slots = [None, None]
 
+    # COCO numbers without pycocotools (test.py:256-278): annotations are read before the loop
+    anno_json = getattr(opt, 'anno_json', None) or './coco/annotations/instances_val2017.json'
+    evaluator = None
+    if save_json and os.path.isfile(anno_json):
+        try:
+            import pycocotools  # noqa: F401
+        except ImportError:
+            from utils.cocoeval import CocoEvaluator, CocoGt
+            ids = [int(Path(x).stem) for x in dataloader.dataset.img_files] if is_coco else None
+            evaluator = CocoEvaluator(CocoGt(anno_json), is_coco, device, img_ids=ids)
+
+    def image_id(path):
+        stem = Path(path).stem
+        return int(stem) if stem.isnumeric() else stem
+
     def enqueue(k, img, targets, paths, shapes, counts):
         """Batch k onto the stream; returns its slot.  Nothing here waits for the device."""
         img = img.to(device, non_blocking=True)
@@ -194,12 +218,17 @@ def test(data,
         correct, _ = match_batch(det, cnt, t_dev, off, descs, (height, width), iouv)
         if plots:   # test.py:188-189 for the whole batch, behind the matching launch
             confusion_matrix.process_batches(det, cnt, t_dev, off, descs, (height, width))
+        if evaluator is not None:   # COCOeval.evaluateImg for the whole batch, behind the same launches
+            flags, rank = evaluator.add_batch(det, cnt, [image_id(p) for p in paths])
         slot = slots[k % 2]
         if slot is None or not slot.fits(nb) or slot.det.shape[1] != det.shape[1]:
-            slot = slots[k % 2] = _Slot(max(nb, batch_size), det.shape[1], niou)
+            slot = slots[k % 2] = _Slot(max(nb, batch_size), det.shape[1], niou, coco=evaluator is not None)
         slot.count[:nb].copy_(cnt, non_blocking=True)
         slot.det[:nb].copy_(det, non_blocking=True)
         slot.correct[:nb].copy_(correct, non_blocking=True)
+        if evaluator is not None:
+            slot.flags[:nb].copy_(flags, non_blocking=True)
+            slot.rank[:nb].copy_(rank, non_blocking=True)
         if t_host is None:
             t_host = torch.empty(t_dev.shape, dtype=torch.float32, pin_memory=True)
             t_host.copy_(t_dev, non_blocking=True)
@@ -213,6 +242,9 @@ def test(data,
         slot.event.synchronize()
         counts = slot.count[:slot.nb].tolist()
         tcol, tclass = slot.targets[:, 0], slot.targets[:, 1]
+        if evaluator is not None:
+            evaluator.update([image_id(p) for p in slot.paths[:slot.nb]], slot.det[:slot.nb].numpy(), counts,
+                             slot.flags[:slot.nb].numpy(), slot.rank[:slot.nb].numpy())
         for si, n in enumerate(counts):
             tcls = tclass[tcol == si].tolist()
             path = Path(slot.paths[si])
@@ -231,11 +263,10 @@ def test(data,
                         line = tuple(row) if save_conf else tuple(row[:5])
                         f.write(('%g ' * len(line)).rstrip() % line + '\n')
             if save_json:   # test.py:168-177
-                image_id = int(path.stem) if path.stem.isnumeric() else path.stem
                 box = xyxy2xywh(predn[:, :4])
                 box[:, :2] -= box[:, 2:] / 2   # xy center to top-left corner
                 for pr, b in zip(predn.tolist(), box.tolist()):
-                    jdict.append({'image_id': image_id,
+                    jdict.append({'image_id': image_id(path),
                                   'category_id': coco91class[int(pr[5])] if is_coco else int(pr[5]),
                                   'bbox': [round(x, 3) for x in b],
                                   'score': round(pr[4], 5)})
@@ -282,25 +313,28 @@ def test(data,
 
     if save_json and len(jdict):   # test.py:256-278
         w = Path(weights[0] if isinstance(weights, list) else weights).stem if weights is not None else ''
-        anno_json = './coco/annotations/instances_val2017.json'
         pred_json = str(save_dir / f'{w}_predictions.json')
         print('\nEvaluating pycocotools mAP... saving %s...' % pred_json)
         with open(pred_json, 'w') as f:
             json.dump(jdict, f)
-        try:
-            from pycocotools.coco import COCO
-            from pycocotools.cocoeval import COCOeval
-            anno = COCO(anno_json)
-            pred = anno.loadRes(pred_json)
-            ev = COCOeval(anno, pred, 'bbox')
-            if is_coco:
-                ev.params.imgIds = [int(Path(x).stem) for x in dataloader.dataset.img_files]
-            ev.evaluate()
-            ev.accumulate()
-            ev.summarize()
-            map, map50 = ev.stats[:2]   # update results (mAP@0.5:0.95, mAP@0.5)
-        except Exception as e:
-            print(f'pycocotools unable to run: {e}')
+        if evaluator is not None:   # pycocotools cannot be imported: its bbox COCOeval, restated
+            evaluator.accumulate()
+            map, map50 = evaluator.summarize()[:2]   # update results (mAP@0.5:0.95, mAP@0.5)
+        else:
+            try:
+                from pycocotools.coco import COCO
+                from pycocotools.cocoeval import COCOeval
+                anno = COCO(anno_json)
+                pred = anno.loadRes(pred_json)
+                ev = COCOeval(anno, pred, 'bbox')
+                if is_coco:
+                    ev.params.imgIds = [int(Path(x).stem) for x in dataloader.dataset.img_files]
+                ev.evaluate()
+                ev.accumulate()
+                ev.summarize()
+                map, map50 = ev.stats[:2]   # update results (mAP@0.5:0.95, mAP@0.5)
+            except Exception as e:
+                print(f'pycocotools unable to run: {e}')
 
     model.float()   # for training
     if not training:
@@ -331,7 +365,11 @@ def parse_opt(argv=None):
     parser.add_argument('--save-txt', action='store_true', help='save results to *.txt')
     parser.add_argument('--save-hybrid', action='store_true', help='unsupported: label+prediction hybrid results')
     parser.add_argument('--save-conf', action='store_true', help='save confidences in --save-txt labels')
-    parser.add_argument('--save-json', action='store_true', help='save a cocoapi-compatible JSON results file')
+    parser.add_argument('--save-json', action='store_true', help='save a cocoapi-compatible JSON results file and, '
+                        'with the annotation file at hand, report the COCO bbox mAP (pycocotools if importable, '
+                        'else the built-in restatement on the device)')
+    parser.add_argument('--anno-json', type=str, default='./coco/annotations/instances_val2017.json',
+                        help='COCO annotation file for --save-json')
     parser.add_argument('--project', default='runs/test', help='save to project/name')
     parser.add_argument('--name', default='exp', help='save to project/name')
     parser.add_argument('--exist-ok', action='store_true', help='existing project/name ok, do not increment')

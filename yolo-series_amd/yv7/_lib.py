@@ -113,6 +113,8 @@ SIGNATURES = {
     'yv7_confusion_ws_bytes': (_sz, [_i, _i, _i]),
     'yv7_confusion': (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, ctypes.POINTER(ScaleDesc), _i, _i, _f, _f, _i, _vp, _vp,
                            _sz, _vp]),
+    'yv7_coco_match_ws_bytes': (_sz, [_i, _i, _i]),
+    'yv7_coco_match': (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     'yv7_draw_ws_bytes': (_sz, [_i, _i]),
     'yv7_draw_boxes': (_i, [ctypes.POINTER(DrawImage), _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i,
                             ctypes.POINTER(GlyphAtlas), _i, _i, _vp, _sz, _vp]),
