@@ -31,6 +31,9 @@
  *                     batch, into a matrix kept on the device   test.py:137-140,181-189
  *   yv7_coco_match    pycocotools' COCOeval.evaluateImg (bbox)  test.py:256-278: ev.evaluate() of the
  *                     over a batch, on the JSON rows' values    third-party library the reference calls
+ *   yv7_draw_boxes    plot_one_box() over a batch               utils/plots.py:57-68, detect.py:204-238
+ *   yv7_mosaic        plot_images(): the picture grid of a      utils/plots.py:114-190 as called from
+ *                     batch with its labels or predictions      test.py:215-220
  */
 #ifndef YV7_H
 #define YV7_H
@@ -396,6 +399,89 @@ size_t yv7_draw_ws_bytes(int B, int max_det);
 int yv7_draw_boxes(const yv7_draw_image* images, int B, const float* det, const int32_t* count, int max_det,
                    const uint8_t* palette, int npal, const char* names, const int32_t* name_off, int nc,
                    const yv7_glyph_atlas* atlases, int n_atlas, int reverse, void* ws, size_t ws_bytes, void* stream);
+
+/* The picture grid of a batch (replaces utils/plots.py:105-190 plot_images as test.py:215-220 calls it for the
+ * first three batches, on the host, on arrays it first copies back): up to ns * ns images pasted as tiles into one
+ * picture, predictions or labels drawn on it, a caption and a border per tile, and the whole downscaled, in four
+ * launches (two when there are no rows to draw) whatever B, the counts and the number of tiles, and without a host
+ * sync.  Integer-only like yv7_draw_boxes, and defined here, not by cv2.  The host computes the geometry
+ * (plots.py:128-145, 186-187): n <= ns * ns tiles of tile_h x tile_w, tile i at block_x = tile_w * (i / ns),
+ * block_y = tile_h * (i % ns) (column by column); the mosaic is Hs x Ws = ns * tile_h x ns * tile_w.
+ * The paint order, later steps over earlier ones, each step over all tiles in turn:
+ * a. Canvas: uint8 [Hs][Ws][3], every byte 255.
+ * b. Tiles: image i < n of images [B][3][H][W] (planes; in_kind YV7_MOSAIC_U8 as is, _F16 / _F32 in [0, 1] become
+ *    clamp(trunc((float)x * 255.0f), 0, 255) with NaN -> 0, the product rounded to fp32) read as an HWC pixel and
+ *    pasted at its block: as is when (tile_h, tile_w) == (H, W), else resized by the letterbox's rule bit for bit
+ *    (yv7_letterbox's resize: cv2's 8-bit INTER_LINEAR with its exact-2x INTER_AREA fast path and the SIMD
+ *    vertical pass's rounding split at tile_w * 3 / 16 * 16).
+ * c. Rows, in the order tile 0 .. n - 1 and within a tile row 0 .. last, each drawn exactly as yv7_draw_boxes draws
+ *    a row (outline, label background, glyph cells, truncation toward zero, a non-finite value or a negative class
+ *    draws nothing, a class >= nc or names == NULL draws a box without a label) with thickness 3, the one atlas,
+ *    and clipped to the whole mosaic, not to the tile.  The row's corners are computed in fp32, every product and
+ *    sum rounded on its own (no FMA); scaled means sf < 1, and (float)sf is the factor.
+ *    Predictions (det != NULL): det [B][max_det][6], count [B] in canvas pixels (before yv7_scale_boxes).  Row
+ *      r < clamp(count[i], 0, max_det) of image i < n is drawn iff conf > 0.25f.  Each corner is v * (float)sf if
+ *      scaled, then + (float)block_x (x1, x2) or + (float)block_y (y1, y2).  Label "name d.d": the digits are
+ *      n = rint((double)conf * 10) clamped to [0, 10], written n / 10, '.', n % 10.
+ *    Labels (label_off != NULL): targets [L][6] rows (image, class, x, y, w, h), label_off [B + 1]; image i's rows
+ *      are label_off[i] .. label_off[i + 1], clamped to [0, L]; label_off must not decrease (a row that two tiles
+ *      claim goes to the first) and column 0 is not read.  Corners x - w / 2, x + w / 2, y - h / 2, y + h / 2;
+ *      with normalized != 0 times (float)tile_w (x) or (float)tile_h (y), else times (float)sf if scaled; then the
+ *      block offset.  Label "name".  The row's confidence counts as 1.
+ *    det and label_off both NULL: no rows.
+ * d. Captions (captions and cap_off may both be NULL): tile i's bytes are captions[cap_off[i] .. cap_off[i + 1]),
+ *    offsets clamped to [0, cap_bytes].  Glyph cells from pen x = block_x + 5 on rows block_y + 5 ..
+ *    block_y + 5 + cell_h - 1, each cell as wide as its advance; a cell pixel of coverage a becomes, per channel,
+ *    (a * 220 + (255 - a) * dst + 127) / 255 over whatever is there.  No background; clipped to the mosaic; tiles
+ *    in order, so a caption that runs into a later tile's caption is blended first.
+ * e. Borders: for every tile, with X0 = block_x, X1 = block_x + tile_w, Y0 = block_y, Y1 = block_y + tile_h, a
+ *    pixel becomes (255, 255, 255) when (|x - X0| <= 1 or |x - X1| <= 1) and Y0 - 1 <= y <= Y1 + 1, or when
+ *    (|y - Y0| <= 1 or |y - Y1| <= 1) and X0 - 1 <= x <= X1 + 1.  Clipped to the mosaic.
+ * f. Output: out uint8 [out_h][out_w][3], Hs / YV7_MOSAIC_MAX_RATIO <= out_h <= Hs and likewise out_w (one thread
+ *    sums an output pixel's whole footprint, so the ratio is bounded: a smaller output is refused; plot_images'
+ *    own ratio is at most ns).  Equal sizes: a copy.  Otherwise the
+ *    exact box filter, with Ws, Hs the mosaic's and Wd, Hd the output's size:
+ *      wx(X, x) = max(0, min((X + 1) * Ws, (x + 1) * Wd) - max(X * Ws, x * Wd)), wy(Y, y) likewise,
+ *      out[Y][X][c] = (sum_y sum_x wy * wx * S[y][x][c] + Ws * Hs / 2) / (Ws * Hs) in integers
+ *    (an exact 2x is (a + b + c + d + 2) >> 2; 3:2 has the weights (2, 1) / (1, 2)).  The sum is bounded by
+ *    255 * Ws * Hs + Ws * Hs / 2: with both sides at most YV7_MOSAIC_MAX_SIDE = 16384 a row's inner sum fits
+ *    32 bits and the whole 64; larger mosaics are refused.
+ * All device inputs are read-only.  ws: device scratch of at least yv7_mosaic_ws_bytes(desc) bytes, 16-byte
+ * aligned: the row records (48 bytes each: n * max_det of them, or L), then the canvas.  One thread decides each
+ * stored pixel of every step, so nothing depends on execution order. */
+#define YV7_MOSAIC_U8 0
+#define YV7_MOSAIC_F16 1
+#define YV7_MOSAIC_F32 2
+#define YV7_MOSAIC_MAX_SIDE 16384
+#define YV7_MOSAIC_THICKNESS 3
+#define YV7_MOSAIC_MAX_RATIO 8 /* mosaic side : output side, at most */
+
+typedef struct {
+  const void* images;      /* device [B][3][H][W] of in_kind */
+  int32_t in_kind, B, H, W;
+  int32_t n, ns, tile_h, tile_w;
+  double sf;               /* max_size / max(H, W); the rows are scaled by (float)sf iff sf < 1 */
+  const float* det;        /* predictions: device [B][max_det][6], or NULL */
+  const int32_t* count;    /* device [B] */
+  int32_t max_det;
+  int32_t L;               /* labels: rows of targets */
+  const float* targets;    /* device [L][6]; may be NULL when L == 0 */
+  const int32_t* label_off; /* device [B + 1], or NULL */
+  int32_t normalized;
+  int32_t npal;
+  const uint8_t* palette;  /* device uint8 [npal][3], as yv7_draw_boxes' */
+  const char* names;       /* device bytes, nullable: boxes without labels */
+  const int32_t* name_off; /* device [nc + 1] */
+  int32_t nc;
+  int32_t cap_bytes;       /* the size of captions */
+  const char* captions;    /* device bytes, nullable */
+  const int32_t* cap_off;  /* device [n + 1], nullable with captions */
+  yv7_glyph_atlas atlas;   /* read only with names or captions */
+  int32_t out_h, out_w;
+} yv7_mosaic_desc;
+
+size_t yv7_mosaic_ws_bytes(const yv7_mosaic_desc* desc);
+int yv7_mosaic(const yv7_mosaic_desc* desc, void* out, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -19,14 +19,12 @@
 
 #include <algorithm>
 
+#include "resize_u8.h"
 #include "yv7_kernels.h"
 
 namespace yv7 {
 
 namespace {
-
-constexpr int COEF = 2048;   // INTER_RESIZE_COEF_SCALE
-constexpr int SIMD_LANES = 16;
 
 // tables: per destination column / row, the two source indices (clamped) and two coefficients
 struct LbTab {
@@ -40,35 +38,19 @@ struct LbTab {
   int* cb1;
 };
 
-__device__ __forceinline__ int cv_round(float v) { return (int)rintf(v); }   // cvRound: half to even
-
 __global__ void lb_tables_kernel(LbTab t, int H, int W, int nh, int nw) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < nw) {   // columns: (sx, fx) reset at the borders (resize.cpp, resizeGeneric_ setup)
-    const double scale = 1.0 / ((double)nw / W);
-    float f = (float)((i + 0.5) * scale - 0.5);
-    int s = (int)floorf(f);
-    f -= (float)s;
-    if (s < 0) { s = 0; f = 0.f; }
-    if (s >= W - 1) { s = W - 1; f = 0.f; }
-    t.x0[i] = s;
-    t.x1[i] = min(s + 1, W - 1);
-    t.ca0[i] = cv_round((1.f - f) * (float)COEF);
-    t.ca1[i] = cv_round(f * (float)COEF);
-  } else if (i < nw + nh) {   // rows: fy kept, fetched rows clamped
+  if (i < nw) {
+    const ResizeTap c = resize_col_tap(i, resize_scale(W, nw), W);
+    t.x0[i] = c.i0; t.x1[i] = c.i1; t.ca0[i] = c.c0; t.ca1[i] = c.c1;
+  } else if (i < nw + nh) {
     const int r = i - nw;
-    const double scale = 1.0 / ((double)nh / H);
-    float f = (float)((r + 0.5) * scale - 0.5);
-    const int s = (int)floorf(f);
-    f -= (float)s;
-    t.y0[r] = min(max(s, 0), H - 1);
-    t.y1[r] = min(max(s + 1, 0), H - 1);
-    t.cb0[r] = cv_round((1.f - f) * (float)COEF);
-    t.cb1[r] = cv_round(f * (float)COEF);
+    const ResizeTap c = resize_row_tap(r, resize_scale(H, nh), H);
+    t.y0[r] = c.i0; t.y1[r] = c.i1; t.cb0[r] = c.c0; t.cb1[r] = c.c1;
   }
 }
 
-// mode: 0 = identity, 1 = bilinear (tables), 2 = exact 2x area
+// mode: resize_mode(); the bilinear one reads the tables
 template <int OUT>
 __global__ void letterbox_kernel(const uint8_t* __restrict__ src, int H, int W, int nh, int nw, int top, int left,
                                  int oh, int ow, uint8_t pb, uint8_t pg, uint8_t pr, int mode, LbTab t,
@@ -81,29 +63,14 @@ __global__ void letterbox_kernel(const uint8_t* __restrict__ src, int H, int W, 
   int v[3];
   if ((unsigned)y < (unsigned)nh && (unsigned)x < (unsigned)nw) {
     const uint8_t* img = src + (size_t)b * H * W * 3;
-    if (mode == 0) {
-      const uint8_t* p = img + ((size_t)y * W + x) * 3;
-      v[0] = p[0]; v[1] = p[1]; v[2] = p[2];
-    } else if (mode == 2) {
-      const uint8_t* p0 = img + ((size_t)(2 * y) * W + 2 * x) * 3;
-      const uint8_t* p1 = p0 + (size_t)W * 3;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) v[c] = (p0[c] + p0[3 + c] + p1[c] + p1[3 + c] + 2) >> 2;
-    } else {
-      const int sx0 = t.x0[x] * 3, sx1 = t.x1[x] * 3, a0 = t.ca0[x], a1 = t.ca1[x];
-      const uint8_t* r0 = img + (size_t)t.y0[y] * W * 3;
-      const uint8_t* r1 = img + (size_t)t.y1[y] * W * 3;
-      const int b0 = t.cb0[y], b1 = t.cb1[y];
-      const int nv = nw * 3 / SIMD_LANES * SIMD_LANES;   // row positions the SIMD vertical pass covers
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const int d0 = r0[sx0 + c] * a0 + r0[sx1 + c] * a1;
-        const int d1 = r1[sx0 + c] * a0 + r1[sx1 + c] * a1;
-        int o;
-        if (x * 3 + c < nv) o = ((((d0 >> 4) * b0) >> 16) + (((d1 >> 4) * b1) >> 16) + 2) >> 2;
-        else o = (d0 * b0 + d1 * b1 + (1 << 21)) >> 22;
-        v[c] = min(max(o, 0), 255);
-      }
+    const auto fetch = [img, W](int yy, int xx, int c) -> int { return img[((size_t)yy * W + xx) * 3 + c]; };
+    if (mode == RESIZE_IDENTITY) {
+      v[0] = fetch(y, x, 0); v[1] = fetch(y, x, 1); v[2] = fetch(y, x, 2);
+    } else if (mode == RESIZE_AREA2X) {
+      resize_area2x_px(fetch, x, y, v);
+    } else {   // the taps from lb_tables_kernel
+      resize_linear_px(fetch, ResizeTap{t.x0[x], t.x1[x], t.ca0[x], t.ca1[x]},
+                       ResizeTap{t.y0[y], t.y1[y], t.cb0[y], t.cb1[y]}, x, nw, v);
     }
   } else {
     v[0] = pb; v[1] = pg; v[2] = pr;
@@ -153,40 +120,9 @@ __global__ void letterbox_ragged_kernel(LbChunk ch, int b0, int oh, int ow, uint
   int v[3];
   if ((unsigned)y < (unsigned)f.nh && (unsigned)x < (unsigned)nw) {
     const uint8_t* img = f.src;
-    if (f.mode == 0) {
-      const uint8_t* p = img + ((size_t)y * W + x) * 3;
-      v[0] = p[0]; v[1] = p[1]; v[2] = p[2];
-    } else if (f.mode == 2) {
-      const uint8_t* q0 = img + ((size_t)(2 * y) * W + 2 * x) * 3;
-      const uint8_t* q1 = q0 + (size_t)W * 3;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) v[c] = (q0[c] + q0[3 + c] + q1[c] + q1[3 + c] + 2) >> 2;
-    } else {
-      // columns: (sx, fx) reset at the borders; rows: fy kept, fetched rows clamped (lb_tables_kernel)
-      float fx = (float)((x + 0.5) * f.sx - 0.5);
-      int s = (int)floorf(fx);
-      fx -= (float)s;
-      if (s < 0) { s = 0; fx = 0.f; }
-      if (s >= W - 1) { s = W - 1; fx = 0.f; }
-      const int sx0 = s * 3, sx1 = min(s + 1, W - 1) * 3;
-      const int a0 = cv_round((1.f - fx) * (float)COEF), a1 = cv_round(fx * (float)COEF);
-      float fy = (float)((y + 0.5) * f.sy - 0.5);
-      const int r = (int)floorf(fy);
-      fy -= (float)r;
-      const uint8_t* r0 = img + (size_t)min(max(r, 0), H - 1) * W * 3;
-      const uint8_t* r1 = img + (size_t)min(max(r + 1, 0), H - 1) * W * 3;
-      const int c0 = cv_round((1.f - fy) * (float)COEF), c1 = cv_round(fy * (float)COEF);
-      const int nv = nw * 3 / SIMD_LANES * SIMD_LANES;   // this frame's SIMD-covered row positions
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const int d0 = r0[sx0 + c] * a0 + r0[sx1 + c] * a1;
-        const int d1 = r1[sx0 + c] * a0 + r1[sx1 + c] * a1;
-        int o;
-        if (x * 3 + c < nv) o = ((((d0 >> 4) * c0) >> 16) + (((d1 >> 4) * c1) >> 16) + 2) >> 2;
-        else o = (d0 * c0 + d1 * c1 + (1 << 21)) >> 22;
-        v[c] = min(max(o, 0), 255);
-      }
-    }
+    // the taps lb_tables_kernel would store, computed inline (the row pair is the same for a whole block)
+    resize_px([img, W](int yy, int xx, int c) -> int { return img[((size_t)yy * W + xx) * 3 + c]; }, f.mode, H, W,
+              nw, f.sx, f.sy, x, y, v);
   } else {
     v[0] = p0; v[1] = p1; v[2] = p2;
   }
@@ -220,11 +156,9 @@ hipError_t launch_letterbox_ragged(const RaggedFrame* frames, int B, int oh, int
       LbFrame& f = ch.f[i];
       f.src = r.src;
       f.H = r.H; f.W = r.W; f.nh = r.nh; f.nw = r.nw; f.top = r.top; f.left = r.left;
-      f.sx = 1.0 / ((double)r.nw / r.W);
-      f.sy = 1.0 / ((double)r.nh / r.H);
-      f.mode = 1;
-      if (r.nh == r.H && r.nw == r.W) f.mode = 0;
-      else if (r.W == 2 * r.nw && r.H == 2 * r.nh) f.mode = 2;
+      f.sx = resize_scale(r.W, r.nw);
+      f.sy = resize_scale(r.H, r.nh);
+      f.mode = resize_mode(r.H, r.W, r.nh, r.nw);
       f.reserved = 0;
     }
     const dim3 grid((ow + 127) / 128, oh, n);
@@ -249,10 +183,8 @@ hipError_t launch_letterbox(const uint8_t* src, int B, int H, int W, int nh, int
                             int ow, const uint8_t pad[3], int out_kind, void* dst, void* ws, hipStream_t st) {
   int* w = reinterpret_cast<int*>(ws);
   LbTab t{w, w + nw, w + 2 * nw, w + 3 * nw, w + 4 * nw, w + 4 * nw + nh, w + 4 * nw + 2 * nh, w + 4 * nw + 3 * nh};
-  int mode = 1;
-  if (nh == H && nw == W) mode = 0;
-  else if (W == 2 * nw && H == 2 * nh) mode = 2;
-  if (mode == 1) {
+  const int mode = resize_mode(H, W, nh, nw);
+  if (mode == RESIZE_LINEAR) {
     const int n = nw + nh;
     hipLaunchKernelGGL(lb_tables_kernel, dim3((n + 255) / 256), dim3(256), 0, st, t, H, W, nh, nw);
     hipError_t e = hipGetLastError();

@@ -290,4 +290,86 @@ int yv7_draw_boxes(const yv7_draw_image* images, int B, const float* det, const 
   return 0;
 }
 
+static_assert(YV7_MOSAIC_MAX_SIDE == yv7::MOSAIC_MAX_SIDE && YV7_MOSAIC_THICKNESS == yv7::MOSAIC_THICKNESS,
+              "the mosaic kernels' constants mirror the header's");
+
+// the descriptor's checks that need no workspace; fills a
+static int mosaic_check(const yv7_mosaic_desc* d, yv7::MosaicArgs* a) {
+  if (!d) return fail(YV7_E_ARG, "yv7_mosaic: null argument");
+  if (!d->images) return fail(YV7_E_ARG, "yv7_mosaic: null images");
+  if (d->in_kind < YV7_MOSAIC_U8 || d->in_kind > YV7_MOSAIC_F32)
+    return fail(YV7_E_ARG, "yv7_mosaic: in_kind must be YV7_MOSAIC_U8, _F16 or _F32");
+  if (d->B <= 0 || d->H <= 0 || d->W <= 0) return fail(YV7_E_SHAPE, "yv7_mosaic: B, H and W must be positive");
+  if (d->H > (1 << 20) || d->W > (1 << 20)) return fail(YV7_E_SHAPE, "yv7_mosaic: an image side above 2^20");
+  if (d->n <= 0 || d->ns <= 0 || d->tile_h <= 0 || d->tile_w <= 0)
+    return fail(YV7_E_SHAPE, "yv7_mosaic: n, ns, tile_h and tile_w must be positive");
+  if (d->n > d->B) return fail(YV7_E_SHAPE, "yv7_mosaic: n exceeds B");
+  if ((int64_t)d->ns * d->tile_h > YV7_MOSAIC_MAX_SIDE || (int64_t)d->ns * d->tile_w > YV7_MOSAIC_MAX_SIDE)
+    return fail(YV7_E_SHAPE, "yv7_mosaic: the mosaic is too large (a side above 16384)");
+  if ((int64_t)d->n > (int64_t)d->ns * d->ns) return fail(YV7_E_SHAPE, "yv7_mosaic: n exceeds ns * ns");
+  if (!(d->sf > 0.0)) return fail(YV7_E_ARG, "yv7_mosaic: sf must be positive");
+  if (d->out_h <= 0 || d->out_w <= 0) return fail(YV7_E_SHAPE, "yv7_mosaic: out_h and out_w must be positive");
+  if (d->out_h > d->ns * d->tile_h || d->out_w > d->ns * d->tile_w)
+    return fail(YV7_E_SHAPE, "yv7_mosaic: the output is larger than the mosaic");
+  // one thread sums an output pixel's whole footprint: keep it to (ratio + 1)^2 canvas pixels
+  if ((int64_t)d->ns * d->tile_h > (int64_t)YV7_MOSAIC_MAX_RATIO * d->out_h ||
+      (int64_t)d->ns * d->tile_w > (int64_t)YV7_MOSAIC_MAX_RATIO * d->out_w)
+    return fail(YV7_E_SHAPE, "yv7_mosaic: the output is more than 8 times smaller than the mosaic");
+  const bool pred = d->det != nullptr, lab = d->label_off != nullptr;
+  if (pred && (lab || d->targets)) return fail(YV7_E_ARG, "yv7_mosaic: predictions and labels both given");
+  if (pred) {
+    if (!d->count) return fail(YV7_E_ARG, "yv7_mosaic: det without count");
+    if (d->max_det <= 0) return fail(YV7_E_ARG, "yv7_mosaic: max_det must be positive");
+    if ((int64_t)d->n * d->max_det > (1 << 24)) return fail(YV7_E_SHAPE, "yv7_mosaic: more than 2^24 rows");
+  } else if (lab) {
+    if (d->L < 0 || d->L > (1 << 24)) return fail(YV7_E_SHAPE, "yv7_mosaic: L must be in 0..2^24");
+    if (d->L > 0 && !d->targets) return fail(YV7_E_ARG, "yv7_mosaic: label_off without targets");
+  } else if (d->targets) {
+    return fail(YV7_E_ARG, "yv7_mosaic: targets without label_off");
+  }
+  if (pred || (lab && d->L > 0)) {
+    if (!d->palette) return fail(YV7_E_ARG, "yv7_mosaic: rows without a palette");
+    if (d->npal < 1) return fail(YV7_E_ARG, "yv7_mosaic: npal must be at least 1");
+    if (d->names && !d->name_off) return fail(YV7_E_ARG, "yv7_mosaic: names without name_off");
+    if (d->names && d->nc < 1) return fail(YV7_E_ARG, "yv7_mosaic: nc must be at least 1 with names");
+  }
+  if ((d->captions != nullptr) != (d->cap_off != nullptr))
+    return fail(YV7_E_ARG, "yv7_mosaic: captions and cap_off go together");
+  if (d->captions && d->cap_bytes < 0) return fail(YV7_E_ARG, "yv7_mosaic: cap_bytes must not be negative");
+  if (d->names || d->captions) {
+    if (!d->atlas.metrics || !d->atlas.cover) return fail(YV7_E_ARG, "yv7_mosaic: the atlas has a null pointer");
+    if (d->atlas.cell_h <= 0 || d->atlas.total_w <= 0 || d->atlas.cell_h > 4096)
+      return fail(YV7_E_SHAPE, "yv7_mosaic: the atlas has a non-positive size or more than 4096 rows");
+  }
+  a->g = {d->n, d->ns, d->tile_h, d->tile_w};
+  a->images = d->images;
+  a->in_kind = d->in_kind; a->B = d->B; a->H = d->H; a->W = d->W;
+  a->sf = d->sf;
+  a->det = d->det; a->count = d->count; a->max_det = d->max_det;
+  a->targets = d->targets; a->label_off = d->label_off; a->L = d->L; a->normalized = d->normalized != 0;
+  a->palette = d->palette; a->npal = d->npal;
+  a->names = reinterpret_cast<const uint8_t*>(d->names); a->name_off = d->name_off; a->nc = d->nc;
+  a->captions = reinterpret_cast<const uint8_t*>(d->captions); a->cap_off = d->cap_off; a->cap_bytes = d->cap_bytes;
+  a->atlas = {d->atlas.metrics, d->atlas.cover, d->atlas.cell_h, d->atlas.total_w};
+  a->out_h = d->out_h; a->out_w = d->out_w;
+  return 0;
+}
+
+size_t yv7_mosaic_ws_bytes(const yv7_mosaic_desc* desc) {
+  yv7::MosaicArgs a;
+  if (mosaic_check(desc, &a)) return 0;
+  return yv7::mosaic_ws_bytes(a);
+}
+
+int yv7_mosaic(const yv7_mosaic_desc* desc, void* out, void* ws, size_t ws_bytes, void* stream) {
+  yv7::MosaicArgs a;
+  if (int rc = mosaic_check(desc, &a)) return rc;
+  if (!out || !ws) return fail(YV7_E_ARG, "yv7_mosaic: null argument");
+  if (ws_bytes < yv7::mosaic_ws_bytes(a)) return fail(YV7_E_WORKSPACE, "yv7_mosaic: workspace too small");
+  if (reinterpret_cast<uintptr_t>(ws) % 16 != 0) return fail(YV7_E_ARG, "yv7_mosaic: ws must be 16-byte aligned");
+  hipError_t e = yv7::launch_mosaic(a, reinterpret_cast<uint8_t*>(out), ws, reinterpret_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return hip_fail(e, "yv7_mosaic launch");
+  return 0;
+}
+
 }  // extern "C"

@@ -389,5 +389,35 @@ size_t draw_ws_bytes(int B, int max_det);
 hipError_t launch_draw_boxes(const DrawImage* images, int B, const float* det, const int32_t* count, int max_det,
                              const uint8_t* palette, int npal, const uint8_t* names, const int32_t* name_off, int nc,
                              const DrawAtlas* atlases, int n_atlas, int reverse, void* ws, hipStream_t st);
+// mosaic.hip: the checked contents of a yv7_mosaic_desc
+constexpr int MOSAIC_THICKNESS = 3, MOSAIC_MAX_SIDE = 16384;
+struct MosaicGeom {
+  int32_t n, ns, tile_h, tile_w;
+};
+struct MosaicArgs {
+  MosaicGeom g;
+  const void* images;
+  int in_kind, B, H, W;
+  double sf;
+  const float* det;
+  const int32_t* count;
+  int max_det;
+  const float* targets;
+  const int32_t* label_off;
+  int L, normalized;
+  const uint8_t* palette;
+  int npal;
+  const uint8_t* names;
+  const int32_t* name_off;
+  int nc;
+  const uint8_t* captions;
+  const int32_t* cap_off;
+  int cap_bytes;
+  DrawAtlas atlas;
+  int out_h, out_w;
+};
+int mosaic_records(const MosaicArgs& a);
+size_t mosaic_ws_bytes(const MosaicArgs& a);
+hipError_t launch_mosaic(const MosaicArgs& a, uint8_t* out, void* ws, hipStream_t st);
 
 }  // namespace yv7

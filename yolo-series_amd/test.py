@@ -22,11 +22,16 @@ is read from the device once, there.  One deliberate deviation: called with a `m
 default, test() writes no files (the reference would drop the five PNGs into the working directory); the matrix
 is still accumulated.
 
-Not here: the test_batch*_labels.jpg / _pred.jpg pictures and W&B logging (`wandb_logger`, `trace` are accepted
-and ignored), `save_hybrid` and `compute_loss` (NotImplementedError), --task study, dataset download, COCO
-segmentation and keypoint evaluation (the restated COCOeval is the bbox one).  Without
-checkpoints at hand `--cfg NAME --synthetic-seed S` builds seeded synthetic weights like detect.py.  There is no
-CPU path.
+With `plots` the first three batches also give the reference's test_batch{0,1,2}_labels.jpg and _pred.jpg
+(test.py:215-220): plot_images builds both picture grids on the stream (one yv7_mosaic call each, from the batch,
+the label rows and nms_batched's det / count before scale_boxes rewrites them), they travel in pinned buffers
+behind the slot's event, and the host only encodes the JPEGs when it consumes the batch.  The pictures follow the
+contract in include/yv7.h, not cv2's rendering.
+
+Not here: W&B logging (`wandb_logger`, `trace` are accepted and ignored), `save_hybrid` and `compute_loss`
+(NotImplementedError), --task study, dataset download, COCO segmentation and keypoint evaluation (the restated
+COCOeval is the bbox one).  Without checkpoints at hand `--cfg NAME --synthetic-seed S` builds seeded synthetic
+weights like detect.py.  There is no CPU path.
 
     python test.py --data data.yaml --cfg yolov7-tiny --img-size 640 --batch-size 32
 """
@@ -48,6 +53,7 @@ from utils.datasets import ValLoader, create_dataloader  # noqa: E402
 from utils.general import (check_dataset, check_file, check_img_size, coco80_to_coco91_class,  # noqa: E402
                            increment_path, nms_batched, scale_boxes, xyxy2xywh)
 from utils.metrics import ConfusionMatrix, ap_per_class, match_batch  # noqa: E402
+from utils.plots import mosaic_tables, plot_images  # noqa: E402
 from utils.torch_utils import select_device  # noqa: E402
 
 # what the reference reads from its global `opt` when called directly (test.py:51, 54, 90); the CLI replaces it
@@ -70,6 +76,7 @@ class _Slot:
         self.rank = torch.empty((nb, max_det), dtype=torch.int32, pin_memory=True) if coco else None
         self.event = torch.cuda.Event()
         self.targets = self.paths = self.shapes = None
+        self.mosaics = None   # (batch index, labels picture, predictions picture) in pinned memory, batches 0..2
 
     def fits(self, nb):
         return self.count.numel() >= nb
@@ -171,6 +178,9 @@ def test(data,
     seen = 0
     confusion_matrix = ConfusionMatrix(nc=nc) if plots else None
     names = {k: v for k, v in enumerate(model.names if hasattr(model, 'names') else model.module.names)}
+    plot_names = [names[k] for k in sorted(names)]
+    if write_plots:
+        mosaic_tables(plot_names, device)   # the pictures' atlas, names and palette: uploaded here, not in enqueue()
     coco91class = coco80_to_coco91_class()
     s = ('%20s' + '%12s' * 6) % ('Class', 'Images', 'Labels', 'P', 'R', 'mAP@.5', 'mAP@.5:.95')
     p, r, mp, mr, map50, map, ap, ap_class = 0., 0., 0., 0., 0., 0., [], []
@@ -195,6 +205,7 @@ def test(data,
     def enqueue(k, img, targets, paths, shapes, counts):
         """Batch k onto the stream; returns its slot.  Nothing here waits for the device."""
         img = img.to(device, non_blocking=True)
+        img_plot = img   # the uint8 batch where the loader supplied one
         if not img.is_floating_point():
             img = (img.half() if half else img.float()) / 255.0   # uint8 to fp16/32, 0 - 255 to 0.0 - 1.0
         elif img.dtype != dtype:
@@ -213,8 +224,15 @@ def test(data,
         timers.append(ev)
         # ratio_pad: gain = ratio[0] and the pads as they stand (general.py:345-346)
         descs = [(int(h0), int(w0), rp[0][0], rp[1][0], rp[1][1]) for (h0, w0), rp in shapes]
-        scale_boxes(det, cnt, descs, views=False)   # native-space pred (test.py:144)
         off = label_offsets(t_dev, nb, counts)
+        mosaics = None
+        if write_plots and k < 3:   # test.py:215-220, on the stream; det is still in canvas pixels here
+            pics = (plot_images(img_plot, t_dev, paths, None, plot_names, label_off=off, normalized=True),
+                    plot_images(img_plot, (det, cnt), paths, None, plot_names))
+            mosaics = (k, *(torch.empty(p.shape, dtype=torch.uint8, pin_memory=True) for p in pics))
+            for host, p in zip(mosaics[1:], pics):
+                host.copy_(p, non_blocking=True)
+        scale_boxes(det, cnt, descs, views=False)   # native-space pred (test.py:144)
         correct, _ = match_batch(det, cnt, t_dev, off, descs, (height, width), iouv)
         if plots:   # test.py:188-189 for the whole batch, behind the matching launch
             confusion_matrix.process_batches(det, cnt, t_dev, off, descs, (height, width))
@@ -234,12 +252,19 @@ def test(data,
             t_host.copy_(t_dev, non_blocking=True)
         slot.event.record()
         slot.targets, slot.paths, slot.shapes, slot.nb = t_host, paths, shapes, nb
+        slot.mosaics = mosaics
         return slot
 
     def consume(slot):
         """A finished batch's pinned copies -> the reference's per-image statistics and side outputs."""
         nonlocal seen
         slot.event.synchronize()
+        if slot.mosaics is not None:
+            from PIL import Image
+            k, labels_pic, pred_pic = slot.mosaics
+            Image.fromarray(labels_pic.numpy()).save(save_dir / f'test_batch{k}_labels.jpg')
+            Image.fromarray(pred_pic.numpy()).save(save_dir / f'test_batch{k}_pred.jpg')
+            slot.mosaics = None
         counts = slot.count[:slot.nb].tolist()
         tcol, tclass = slot.targets[:, 0], slot.targets[:, 1]
         if evaluator is not None:

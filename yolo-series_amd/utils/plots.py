@@ -5,9 +5,14 @@ launches per 64 images) on nms_batched's fixed-shape output after scale_boxes, s
 The drawing is defined by the contract in include/yv7.h, not by cv2 (absent here): square corners, no anti-aliased
 edges, and the text comes from PIL's default font rendered once into a glyph atlas.  There is no CPU path and no
 plot_one_box for one box on a host array.
+
+`plot_images(images, targets, paths, fname, names, ...)` is the reference's picture grid (plots.py:114-190, the
+test_batch*_labels.jpg / _pred.jpg of test.py) built on the device by one yv7_mosaic call, and `output_to_target`
+its host helper (plots.py:105-111).
 """
 from __future__ import annotations
 
+import ctypes
 import math
 
 import numpy as np
@@ -192,4 +197,170 @@ def plot_boxes(frames, det, count, names=None, colors=None, line_thickness=None,
                                 arr if atlases else None, len(atlases), int(bool(reverse)), ws.data_ptr(),
                                 ws.numel(), stream)
     L.check(rc, 'yv7_draw_boxes')
+    return out
+
+
+def mosaic_geometry(bs, h, w, max_size=640, max_subplots=16, max_out=1280):
+    """The picture grid's sizes with plot_images' own float expressions (plots.py:128-145, 186-187).  max_out is the
+    reference's constant 1280.  Returns a dict: n tiles on an ns x ns grid, tile (h, w), sf, mosaic (h, w),
+    out (h, w) and blocks [(block_x, block_y)] per tile (tiles fill column by column)."""
+    n = min(int(bs), int(max_subplots))
+    ns = np.ceil(n ** 0.5)
+    sf = max_size / max(h, w)
+    if sf < 1:
+        h = math.ceil(sf * h)
+        w = math.ceil(sf * w)
+    r = min(float(max_out) / max(h, w) / ns, 1.0)
+    return dict(n=n, ns=int(ns), sf=float(sf), tile=(h, w), mosaic=(int(ns * h), int(ns * w)),
+                out=(int(ns * h * r), int(ns * w * r)),
+                blocks=[(int(w * (i // ns)), int(h * (i % ns))) for i in range(n)])
+
+
+def output_to_target(output):
+    """plots.py:105-111: NMS output -> [n, 7] numpy rows (batch_id, class_id, x, y, w, h, conf).  output: a list of
+    per-image [k, 6] tensors, or nms_batched's (det, count) pair.  A host function (it reads the device)."""
+    if isinstance(output, tuple) and len(output) == 2 and getattr(output[0], 'ndim', 0) == 3:
+        det, count = output
+        output = [det[i, :max(min(int(c), det.shape[1]), 0)] for i, c in enumerate(count.tolist())]
+    targets = []
+    for i, o in enumerate(output):
+        o = o.cpu().numpy() if isinstance(o, torch.Tensor) else np.asarray(o)
+        for *box, conf, cls in o:
+            x1, y1, x2, y2 = box
+            targets.append([i, cls, (x1 + x2) / 2, (y1 + y2) / 2, x2 - x1, y2 - y1, conf])
+    return np.array(targets)
+
+
+def _upload(arr, device):
+    """A host array to the device from pinned memory, without waiting for it."""
+    return torch.from_numpy(np.ascontiguousarray(arr)).pin_memory().to(device, non_blocking=True)
+
+
+def _host_targets(targets, n_img, device):
+    """The reference's host rows, grouped by image with a stable sort: [n, 6] labels -> ('labels', rows, label_off);
+    [n, 7] predictions (x, y, w, h in pixels, conf last) -> ('pred', det [B, max_det, 6], count)."""
+    t = targets.cpu().numpy() if isinstance(targets, torch.Tensor) else np.asarray(targets)
+    t = np.asarray(t, np.float32)
+    if t.ndim != 2 or t.shape[1] not in (6, 7):
+        raise ValueError(f'plot_images: host targets must be [n, 6] or [n, 7], got {t.shape}')
+    img = t[:, 0].astype(np.int64)
+    t, img = t[(img >= 0) & (img < n_img)], img[(img >= 0) & (img < n_img)]
+    order = np.argsort(img, kind='stable')
+    t, img = t[order], img[order]
+    per = np.bincount(img, minlength=n_img)
+    off = np.concatenate(([0], np.cumsum(per))).astype(np.int32)
+    if t.shape[1] == 6:
+        return 'labels', _upload(t, device), _upload(off, device)
+    max_det = max(int(per.max()) if len(per) else 0, 1)
+    det = np.zeros((n_img, max_det, 6), np.float32)
+    hw, hh = t[:, 4] / np.float32(2), t[:, 5] / np.float32(2)
+    rows = np.stack([t[:, 2] - hw, t[:, 3] - hh, t[:, 2] + hw, t[:, 3] + hh, t[:, 6], t[:, 1]], 1)
+    for b in range(n_img):
+        det[b, :per[b]] = rows[off[b]:off[b + 1]]
+    return 'pred', _upload(det, device), _upload(per.astype(np.int32), device)
+
+
+def mosaic_tables(names, device, atlas=None):
+    """(palette, (names blob, offsets, nc), atlas) on the device, as plot_images passes them on.  They are cached:
+    the first use uploads them (and waits for that), so a caller that must not wait calls this ahead of time."""
+    device = _hip_device(device)
+    if isinstance(names, dict):   # {index: name}
+        names = [names.get(i, str(i)) for i in range(max(names) + 1)] if names else None
+    if atlas is None:
+        atlas = glyph_atlas(text_height(L.MOSAIC_THICKNESS), device)
+    return (_palette(color_list(), device), _names_blob(names if names else [str(i) for i in range(1024)], device),
+            atlas)
+
+
+def plot_images(images, targets, paths=None, fname='images.jpg', names=None, max_size=640, max_subplots=16, *,
+                label_off=None, normalized=True, max_out=1280, atlas=None):
+    """plot_images (plots.py:114-190) on the device: one yv7_mosaic call (four launches) builds the picture grid of
+    the batch's first max_subplots images with boxes, captions and borders, downscaled to at most max_out pixels.
+
+    images: HIP tensor [B, 3, H, W], uint8 or fp16 / fp32 in [0, 1].  targets: a (det, count) pair on the device
+    (nms_batched's, in canvas pixels: predictions, drawn above conf 0.25 as 'name d.d'); a device [L, 6] tensor
+    (image, class, x, y, w, h) sorted by image, with label_off [B + 1] (counted on the device if None), `normalized`
+    saying whether xywh are fractions of the image or pixels: labels, drawn as 'name'; a host array or tensor in
+    the reference's [n, 6] / [n, 7] format; or None / empty.  names=None labels with the class index.  paths: the
+    captions, Path(p).name[:40].  The contract is in include/yv7.h; the picture is not cv2's.
+    Returns the picture as a device uint8 [out_h, out_w, 3] tensor, stream-ordered; with fname it is also saved
+    with PIL, the one host read (fname=None reads nothing back)."""
+    if not (isinstance(images, torch.Tensor) and images.is_cuda):
+        raise RuntimeError('plot_images draws on a ROCm device (libyv7); got CPU images')
+    kinds = {torch.uint8: L.MOSAIC_U8, torch.float16: L.MOSAIC_F16, torch.float32: L.MOSAIC_F32}
+    if images.dim() != 4 or images.shape[1] != 3 or images.dtype not in kinds or images.shape[0] == 0:
+        raise ValueError(f'plot_images: expected uint8 / fp16 / fp32 images [B, 3, H, W], got {images.dtype} '
+                         f'{tuple(images.shape)}')
+    device = images.device
+    images = images.contiguous()
+    B, _, H, W = images.shape
+    geo = mosaic_geometry(B, H, W, max_size, max_subplots, max_out)
+    n = geo['n']
+
+    d = L.MosaicDesc()
+    d.images, d.in_kind, d.B, d.H, d.W = images.data_ptr(), kinds[images.dtype], B, H, W
+    d.n, d.ns, (d.tile_h, d.tile_w), d.sf = n, geo['ns'], geo['tile'], geo['sf']
+    d.out_h, d.out_w = geo['out']
+    d.normalized = int(bool(normalized))
+    keep = [images]
+
+    kind = None
+    if isinstance(targets, tuple):
+        kind, (det, count) = 'pred', targets
+    elif isinstance(targets, torch.Tensor) and targets.is_cuda:
+        kind, rows = 'labels', targets
+        if label_off is None:   # counted on the device: a comparison and a cumsum, nothing waits
+            per = (rows[:, 0:1] == torch.arange(B, device=device, dtype=rows.dtype)).sum(0, dtype=torch.int32)
+            label_off = torch.cat((torch.zeros(1, dtype=torch.int32, device=device), per.cumsum(0, dtype=torch.int32)))
+    elif targets is not None and len(targets) > 0:
+        kind, a, b = _host_targets(targets, B, device)
+        if kind == 'pred':
+            det, count = a, b
+        else:
+            rows, label_off = a, b
+    if kind == 'pred':
+        if det.dtype != torch.float32 or det.dim() != 3 or det.shape[0] != B or det.shape[2] != 6 or \
+                not det.is_contiguous() or det.device != device:
+            raise ValueError(f'plot_images: expected contiguous fp32 det [B, max_det, 6] for {B} images')
+        if count.dtype != torch.int32 or tuple(count.shape) != (B,) or not count.is_contiguous() or \
+                count.device != device:
+            raise ValueError('plot_images: count must be int32 [B] on the images\' device')
+        d.det, d.count, d.max_det = det.data_ptr(), count.data_ptr(), det.shape[1]
+        keep += [det, count]
+    elif kind == 'labels':
+        if rows.dim() != 2 or rows.shape[1] != 6 or rows.device != device:
+            raise ValueError(f'plot_images: expected labels [L, 6] on the images\' device, got {tuple(rows.shape)}')
+        rows = rows.float().contiguous()
+        if label_off.dtype != torch.int32 or tuple(label_off.shape) != (B + 1,) or not label_off.is_contiguous() or \
+                label_off.device != device:
+            raise ValueError('plot_images: label_off must be int32 [B + 1] on the images\' device')
+        d.L, d.targets, d.label_off = rows.shape[0], rows.data_ptr() if rows.shape[0] else None, label_off.data_ptr()
+        keep += [rows, label_off]
+
+    pal, (blob, off, nc), atlas = mosaic_tables(names, device, atlas)
+    d.palette, d.npal, d.names, d.name_off, d.nc = pal.data_ptr(), pal.shape[0], blob.data_ptr(), off.data_ptr(), nc
+    d.atlas.metrics, d.atlas.cover = atlas.metrics.data_ptr(), atlas.cover.data_ptr()
+    d.atlas.cell_h, d.atlas.total_w = atlas.cell_h, atlas.total_w
+    if paths:
+        from pathlib import Path
+        raw = [Path(paths[i]).name[:40].encode('utf-8') if i < len(paths) else b'' for i in range(n)]
+        cap_off = np.concatenate(([0], np.cumsum([len(r) for r in raw]))).astype(np.int32)
+        caps = _upload(np.frombuffer(b''.join(raw) + b'\0', np.uint8).copy(), device)   # never empty
+        cap_off_d = _upload(cap_off, device)
+        d.captions, d.cap_off, d.cap_bytes = caps.data_ptr(), cap_off_d.data_ptr(), int(cap_off[-1])
+        keep += [caps, cap_off_d]
+
+    lib = L.lib()
+    out = torch.empty((d.out_h, d.out_w, 3), dtype=torch.uint8, device=device)
+    need = int(lib.yv7_mosaic_ws_bytes(ctypes.byref(d)))
+    if need == 0:
+        L.check(-1, 'yv7_mosaic_ws_bytes')
+    ws = torch.empty(need, dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        stream = torch.cuda.current_stream(device).cuda_stream
+        rc = lib.yv7_mosaic(ctypes.byref(d), out.data_ptr(), ws.data_ptr(), ws.numel(), stream)
+    L.check(rc, 'yv7_mosaic')
+    if fname:
+        from PIL import Image
+        Image.fromarray(out.cpu().numpy()).save(fname)
     return out

@@ -81,6 +81,24 @@ class GlyphAtlas(ctypes.Structure):
 
 DRAW_MAX_ATLAS, DRAW_TILE_W, DRAW_TILE_H = 8, 64, 32
 
+
+class MosaicDesc(ctypes.Structure):
+    """yv7_mosaic_desc: everything yv7_mosaic reads but the output and the workspace."""
+    _fields_ = [('images', ctypes.c_void_p), ('in_kind', ctypes.c_int32), ('B', ctypes.c_int32),
+                ('H', ctypes.c_int32), ('W', ctypes.c_int32),
+                ('n', ctypes.c_int32), ('ns', ctypes.c_int32), ('tile_h', ctypes.c_int32), ('tile_w', ctypes.c_int32),
+                ('sf', ctypes.c_double),
+                ('det', ctypes.c_void_p), ('count', ctypes.c_void_p), ('max_det', ctypes.c_int32),
+                ('L', ctypes.c_int32), ('targets', ctypes.c_void_p), ('label_off', ctypes.c_void_p),
+                ('normalized', ctypes.c_int32), ('npal', ctypes.c_int32), ('palette', ctypes.c_void_p),
+                ('names', ctypes.c_void_p), ('name_off', ctypes.c_void_p), ('nc', ctypes.c_int32),
+                ('cap_bytes', ctypes.c_int32), ('captions', ctypes.c_void_p), ('cap_off', ctypes.c_void_p),
+                ('atlas', GlyphAtlas), ('out_h', ctypes.c_int32), ('out_w', ctypes.c_int32)]
+
+
+MOSAIC_U8, MOSAIC_F16, MOSAIC_F32 = 0, 1, 2
+MOSAIC_MAX_SIDE, MOSAIC_THICKNESS, MOSAIC_MAX_RATIO = 16384, 3, 8
+
 _vp, _i, _i64, _sz, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float
 
 # name -> (restype, argtypes); every symbol include/yv7.h declares
@@ -118,6 +136,8 @@ SIGNATURES = {
     'yv7_draw_ws_bytes': (_sz, [_i, _i]),
     'yv7_draw_boxes': (_i, [ctypes.POINTER(DrawImage), _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i,
                             ctypes.POINTER(GlyphAtlas), _i, _i, _vp, _sz, _vp]),
+    'yv7_mosaic_ws_bytes': (_sz, [ctypes.POINTER(MosaicDesc)]),
+    'yv7_mosaic': (_i, [ctypes.POINTER(MosaicDesc), _vp, _vp, _sz, _vp]),
 }
 
 _LIB = None
