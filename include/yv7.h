@@ -74,13 +74,15 @@ typedef enum { YV7_ACT_NONE = 0, YV7_ACT_SILU = 1, YV7_ACT_LEAKY = 2 } yv7_act;
 typedef enum { YV7_WFMT_PLAN = 0, YV7_WFMT_FP8 = 1 } yv7_wfmt;
 
 typedef enum {
-  YV7_OP_INPUT = 0,    /* NCHW image batch -> NHWC tensor; k=2 means fused ReOrg space-to-depth */
+  YV7_OP_INPUT = 0,    /* NCHW image batch -> NHWC tensor; k=2 means fused ReOrg space-to-depth; cout = the
+                          image's channels C (k=2: 4 C), 1 .. the tensor's channels (0: the 3-channel image) */
   YV7_OP_CONV = 1,     /* k x k conv, stride s, pad, + fp32 bias + act; NHWC channel slices in/out */
   YV7_OP_MAXPOOL = 2,  /* max pool k, stride s, pad (implicit -inf padding) */
   YV7_OP_UPSAMPLE = 3, /* nearest-neighbour x2 */
   YV7_OP_COPY = 4,     /* channel-slice copy (concat input that could not be written in place) */
   YV7_OP_DETECT = 5,   /* 1x1 conv + bias + sigmoid + grid/anchor decode -> z rows, raw logits */
-  YV7_OP_STEM = 6,     /* fp16: image -> conv A (3->32, 3x3, stride s) -> conv B (32->64, 3x3, s2), A kept in LDS;
+  YV7_OP_STEM = 6,     /* fp16: image -> conv A (cin->32, 3x3, stride s) -> conv B (32->64, 3x3, s2), A kept in LDS;
+                          cin = the image's channels, 1..4 (weights K = tap*cin + ci);
                           cin 12: the yolov7-w6 front end, image -> ReOrg (common.py:48-53) -> conv A (12->64,
                           3x3, s1; weights K = tap*16 + ci) -> conv B (64->128, 3x3, s2) */
   YV7_OP_ADD = 7       /* dst = src + src2 over cout channels (Shortcut, common.py:80-86): three channel slices with
@@ -139,7 +141,7 @@ int yv7_plan_create(const yv7_net_desc* desc, const void* weights, size_t nbytes
                     yv7_plan** out);
 void yv7_plan_destroy(yv7_plan* plan);
 
-/* Bytes of caller-provided workspace yv7_forward needs for a [B,3,H,W] batch. */
+/* Bytes of caller-provided workspace yv7_forward needs for a [B,C,H,W] batch. */
 size_t yv7_workspace_bytes(const yv7_plan* plan, int B, int H, int W);
 /* Hand workspace memory [ws, ws + bytes) back to the caller: the next yv7_forward on any part of it
  * clears it again. */
@@ -158,14 +160,15 @@ typedef struct {
   int32_t reserved;
 } yv7_row_best;
 
-/* x: [B,3,H,W] (x_dtype f32 or f16, values in [0,1]) on the plan's device.
+/* x: [B,C,H,W] (x_dtype f32 or f16, values in [0,1]) on the plan's device; C is fixed by the plan (its
+ * INPUT op's cout, or its STEM op's cin; 3 for the ReOrg stem) and is not passed: the caller checks it.
  * z_out: [B, N, no] fp32 decoded boxes (Detect z).  raw_out (nullable): per level l the raw head
  * logits [B, na, ny_l, nx_l, no] fp32, levels concatenated.  rowbest_out (nullable): [B, N]
  * yv7_row_best (fp16 plans write it from the head's epilogue).  Asynchronous on `stream`. */
 int yv7_forward(yv7_plan* plan, const void* x, int x_dtype, int B, int H, int W, float* z_out,
                 float* raw_out, yv7_row_best* rowbest_out, void* workspace, size_t ws_bytes, void* stream);
 
-/* The kernels the dispatch launches for every op of a [B,3,H,W] forward, without running it (a dry
+/* The kernels the dispatch launches for every op of a [B,C,H,W] forward, without running it (a dry
  * run of yv7_forward's op loop): one line per op, "op<TAB>kernel[|kernel...]", kernel = the demangled
  * symbol rocprofv3's kernel trace reports.  Lets a caller attribute per-op timings (yv7_profile_read)
  * to kernel families.  x_dtype: the image dtype the forward would get (the INPUT / STEM kernels depend on

@@ -34,6 +34,7 @@ int main(int argc, char** argv) {
   p.variant = argc > 1 ? atoi(argv[1]) : 0;
   p.B = B; p.H = H; p.W = W; p.yc = CB; p.yoff = 0; p.kpad_a = KA; p.kpad_b = KB; p.act_a = 1; p.act_b = 1; p.sa = 1;
   p.reorg = w6;
+  p.cin = w6 ? 12 : 3;
   hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
   for (int i = 0; i < 3; ++i) CK(yv7::launch_stem(p, 1, 0));
   CK(hipDeviceSynchronize());

@@ -29,11 +29,11 @@ template <typename T> __device__ __forceinline__ T tmax(T a, T b) { return a > b
 // Index math is 32-bit throughout (pixel and vector counts of one launch stay far below 2^31; the
 // runtime checks tensor sizes): a 64-bit division costs several times the 16-byte move it addresses.
 
-// ---- input: x [B,3,H,W] (f32 or f16) -> bordered NHWC T [B,H',W',yc], zero-padded channels.
-//      reorg: space-to-depth, channel = g*3 + c, g over (row even,col even),(odd,even),(even,odd),(odd,odd)
+// ---- input: x [B,C,H,W] (f32 or f16) -> bordered NHWC T [B,H',W',yc], zero-padded channels.
+//      reorg: space-to-depth, channel = g*C + c, g over (row even,col even),(odd,even),(even,odd),(odd,odd)
 template <typename T, typename S, bool REORG>
-__global__ __launch_bounds__(NT) void input_kernel(const S* __restrict__ x, T* __restrict__ y, int B, int H, int W,
-                                                   int yc) {
+__global__ __launch_bounds__(NT) void input_kernel(const S* __restrict__ x, T* __restrict__ y, int B, int C, int H,
+                                                   int W, int yc) {
   const int Ho = REORG ? H / 2 : H, Wo = REORG ? W / 2 : W;
   const int npix = B * Ho * Wo;
   const size_t plane = (size_t)H * W;
@@ -41,15 +41,15 @@ __global__ __launch_bounds__(NT) void input_kernel(const S* __restrict__ x, T* _
     const int t = pix / Wo, wo = pix - t * Wo;
     const int b = t / Ho, ho = t - b * Ho;
     T* out = y + pix_index(b, ho, wo, Ho, Wo) * yc;
-    const S* xb = x + (size_t)b * 3 * plane;
+    const S* xb = x + (size_t)b * C * plane;
     if (!REORG) {
       const size_t o = (size_t)ho * W + wo;
-      for (int c = 0; c < yc; ++c) out[c] = c < 3 ? (T)(float)xb[c * plane + o] : (T)0.0f;
+      for (int c = 0; c < yc; ++c) out[c] = c < C ? (T)(float)xb[c * plane + o] : (T)0.0f;
     } else {
       for (int c = 0; c < yc; ++c) {
         T v = (T)0.0f;
-        if (c < 12) {
-          const int gsel = c / 3, ch = c - gsel * 3;
+        if (c < 4 * C) {
+          const int gsel = c / C, ch = c - gsel * C;
           const int dr = gsel & 1, dc = gsel >> 1;   // g0 (0,0) g1 (1,0) g2 (0,1) g3 (1,1)
           v = (T)(float)xb[ch * plane + (size_t)(2 * ho + dr) * W + (2 * wo + dc)];
         }
@@ -280,33 +280,34 @@ __global__ __launch_bounds__(NT) void input_reorg16_kernel(const S* __restrict__
 }
 
 template <typename T, typename S>
-hipError_t input_t(const void* x, void* y, int B, int H, int W, int yc, bool reorg, hipStream_t st) {
+hipError_t input_t(const void* x, void* y, int B, int C, int H, int W, int yc, bool reorg, hipStream_t st) {
   const size_t npix = (size_t)B * (reorg ? (H / 2) * (W / 2) : H * W);
+  if (C < 1 || (reorg ? 4 * C : C) > yc) return hipErrorInvalidValue;
   if constexpr (std::is_same<T, _Float16>::value) {
-    if (reorg && yc == 16) {
+    if (reorg && yc == 16 && C == 3) {   // (the three-plane form: 12 channels + 4 zero as two 16-byte stores)
       YV7_LAUNCH((input_reorg16_kernel<S>), dim3(grid_for(npix)), dim3(NT), 0, st, (const S*)x, (T*)y, B, H,
                          W);
       return hipGetLastError();
     }
   }
   if (reorg)
-    YV7_LAUNCH((input_kernel<T, S, true>), dim3(grid_for(npix)), dim3(NT), 0, st, (const S*)x, (T*)y, B, H,
+    YV7_LAUNCH((input_kernel<T, S, true>), dim3(grid_for(npix)), dim3(NT), 0, st, (const S*)x, (T*)y, B, C, H,
                        W, yc);
   else
-    YV7_LAUNCH((input_kernel<T, S, false>), dim3(grid_for(npix)), dim3(NT), 0, st, (const S*)x, (T*)y, B, H,
+    YV7_LAUNCH((input_kernel<T, S, false>), dim3(grid_for(npix)), dim3(NT), 0, st, (const S*)x, (T*)y, B, C, H,
                        W, yc);
   return hipGetLastError();
 }
 
 }  // namespace
 
-hipError_t launch_input(int dtype, const void* x, int x_dtype, void* y, int B, int H, int W, int yc, bool reorg,
-                        hipStream_t st) {
+hipError_t launch_input(int dtype, const void* x, int x_dtype, void* y, int B, int C, int H, int W, int yc,
+                        bool reorg, hipStream_t st) {
   if (dtype == 1)
-    return x_dtype == 1 ? input_t<_Float16, _Float16>(x, y, B, H, W, yc, reorg, st)
-                        : input_t<_Float16, float>(x, y, B, H, W, yc, reorg, st);
-  return x_dtype == 1 ? input_t<float, _Float16>(x, y, B, H, W, yc, reorg, st)
-                      : input_t<float, float>(x, y, B, H, W, yc, reorg, st);
+    return x_dtype == 1 ? input_t<_Float16, _Float16>(x, y, B, C, H, W, yc, reorg, st)
+                        : input_t<_Float16, float>(x, y, B, C, H, W, yc, reorg, st);
+  return x_dtype == 1 ? input_t<float, _Float16>(x, y, B, C, H, W, yc, reorg, st)
+                      : input_t<float, float>(x, y, B, C, H, W, yc, reorg, st);
 }
 
 hipError_t launch_maxpool(int dtype, const void* x, int B, int H, int W, int xc, int xoff, void* y, int Ho, int Wo,

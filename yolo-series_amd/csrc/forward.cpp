@@ -85,7 +85,7 @@ int find_cascade(const yv7_plan* p, size_t i, const Layout& l, unsigned char* ws
 }
 
 int op_input(const Fwd& f, const yv7_op_desc& o) {
-  return launched(yv7::launch_input(f.p->dtype, f.x, f.x_dtype, f.at(o.dst), f.l.B, f.l.H, f.l.W,
+  return launched(yv7::launch_input(f.p->dtype, f.x, f.x_dtype, f.at(o.dst), f.l.B, input_channels(o), f.l.H, f.l.W,
                                     f.p->tensors[o.dst].channels, o.k == 2, f.st));
 }
 
@@ -176,6 +176,9 @@ int op_stem(const Fwd& f, const yv7_op_desc& o) {
   if ((H >> to.shift) != H / (reorg + 1) / o.s / 2 || (W >> to.shift) != W / (reorg + 1) / o.s / 2 ||
       (reorg && (H % 4 || W % 4)))
     return fail(YV7_E_SHAPE, "yv7_forward: stem output shape mismatch");
+  // the kernels address the image through 32-bit byte offsets, bit 31 marking a pixel outside it
+  if ((size_t)f.l.B * input_channels(o) * H * W * (f.x_dtype == YV7_DT_F16 ? 2 : 4) >= ((size_t)1 << 31))
+    return fail(YV7_E_SHAPE, "yv7_forward: stem input exceeds 2 GiB");
   yv7::StemParams sp;
   sp.variant = 0;
   sp.x = f.x;
@@ -190,7 +193,8 @@ int op_stem(const Fwd& f, const yv7_op_desc& o) {
   sp.yc = to.channels;
   sp.yoff = o.dst_coff;
   sp.reorg = reorg;
-  sp.kpad_a = ((reorg ? 9 * 16 : 27) + 63) / 64 * 64;
+  sp.cin = o.cin;
+  sp.kpad_a = ((reorg ? 9 * 16 : 9 * o.cin) + 63) / 64 * 64;
   sp.kpad_b = (9 * o.cout + 63) / 64 * 64;
   sp.act_a = o.act;
   sp.act_b = o.act2;

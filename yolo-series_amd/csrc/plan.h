@@ -55,10 +55,18 @@ inline int kpad_of(const yv7_op_desc& o) {
   if (is_f8(o)) return (o.cin + 127) / 128 * 128;
   return (o.k * o.k * o.cin + 63) / 64 * 64;
 }
+// Channels an INPUT op packs (cout; k == 2: after the space-to-depth, four per image plane); 0, from a descriptor
+// written before the field was read, stands for the three-plane image
+inline int input_packed(const yv7_op_desc& o) { return o.cout ? o.cout : (o.k == 2 ? 12 : 3); }
+// Planes C of the [B,C,H,W] image an INPUT or STEM op reads (the ReOrg stem, cin 12: three)
+inline int input_channels(const yv7_op_desc& o) {
+  if (o.kind == YV7_OP_STEM) return o.cin == 12 ? 3 : o.cin;
+  return o.k == 2 ? input_packed(o) / 4 : input_packed(o);
+}
 // channel slices [ca, ca + na) of tensor ta and [cb, cb + nb) of tensor tb share a channel
 inline bool overlap(int ta, int ca, int na, int tb, int cb, int nb) { return ta == tb && ca < cb + nb && cb < ca + na; }
 
-// Where a [B,3,H,W] batch's data lies in the workspace (computed per call, plan_layout.cpp).  Tensors: bordered
+// Where a [B,C,H,W] batch's data lies in the workspace (computed per call, plan_layout.cpp).  Tensors: bordered
 // NHWC [B][h + 2*YV7_BORDER][w + 2*YV7_BORDER][C] each, 256-byte aligned.  Behind them the scratch: split-K
 // fp32 partial tiles (the largest any conv of the plan needs; convs run one at a time) and the per-tile arrival
 // counters (zeroed with the workspace, re-armed by the kernels), the dense e4m3 copy of an FP8 op's input (the

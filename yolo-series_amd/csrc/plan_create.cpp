@@ -67,12 +67,20 @@ int validate_op(const yv7_net_desc* d, int i, size_t nbytes) {
     if (o.kind == YV7_OP_DETECT && (o.level < 0 || o.level >= d->nl || o.cout != d->na * d->no || o.k != 1))
       return fail(YV7_E_ARG, "yv7_plan_create: bad detect op");
   }
+  if (o.kind == YV7_OP_INPUT) {
+    // cout: the channels the op packs (plan.h input_packed)
+    const int c = input_packed(o);
+    if (c < 1 || c > d->tensors[o.dst].channels)
+      return fail(YV7_E_ARG, op + " input channels outside 1 .. the destination tensor's channels");
+    if (o.k == 2 && c % 4)
+      return fail(YV7_E_ARG, op + " reorganised input channels not a multiple of 4");
+  }
   if (o.kind == YV7_OP_STEM) {
     if (d->dtype != YV7_DT_F16 || !yv7::stem_supported(o.cin, o.cout, o.cout2, o.s) || o.k != 3 || o.act != o.act2 ||
         o.dst_coff % vec || o.dst_coff + o.cout2 > d->tensors[o.dst].channels)
       return fail(YV7_E_ARG, "yv7_plan_create: unsupported stem op");
-    // cin 12: the w6 front end (ReOrg fused), conv A's K = tap * 16 + ci
-    const int ka = o.cin == 12 ? 9 * 16 : 27;
+    // cin 12: the w6 front end (ReOrg fused), conv A's K = tap * 16 + ci; else K = tap * cin + ci, cin 1 .. 4
+    const int ka = o.cin == 12 ? 9 * 16 : 9 * o.cin;
     const size_t wa = (size_t)o.cout * ((ka + 63) / 64 * 64) * 2, wb = (size_t)o.cout2 * ((9 * o.cout + 63) / 64 * 64) * 2;
     if (o.w_off < 0 || o.w2_off < 0 || (size_t)o.w_off + wa > nbytes || (size_t)o.w2_off + wb > nbytes ||
         (size_t)o.b_off + 4 * o.cout > nbytes || (size_t)o.b2_off + 4 * o.cout2 > nbytes)

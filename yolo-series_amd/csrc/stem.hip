@@ -1,5 +1,6 @@
-// Fused stem for gfx950: image packing + conv A (3 -> CA, 3x3, stride SA) + conv B (CA -> CB, 3x3,
-// stride 2), conv A's activations never leave LDS.
+// Fused stem for gfx950: image packing + conv A (CIN -> CA, 3x3, stride SA) + conv B (CA -> CB, 3x3,
+// stride 2), conv A's activations never leave LDS.  CIN = 3 (RGB), or 1, 2, 4 for Model(cfg, ch=C): grayscale /
+// thermal frames, RGB + IR or depth stacks.
 //
 // Replaces, for the yolov7 / yolov7-tiny stems, the reference's first two Conv layers
 // (models/common.py:110-111 on cfg/deploy/yolov7.yaml:15-17, yolov7-tiny.yaml:14-16) and the input
@@ -8,9 +9,10 @@
 // times through L2 by conv B; fused, it exists only as a 17 x 33 x CA tile in LDS per block.
 //
 // Per 256-thread block: a TBY x TBX tile of conv B's output for one image.
-//   1. the NCHW image patch feeding it (PY x PX x 3, zero outside the image) -> LDS [PY][PX][4] fp16
-//   2. conv A on the MFMA: M = TAY*TAX A-pixels (16 per tile), N = CA, K = 27 (one 16x16x32 step,
-//      k = tap*3 + ci, zero-padded to 32), operands gathered from the patch; + bias + act, zeroed
+//   1. the NCHW image patch feeding it (PY x PX x CIN, zero outside the image) -> LDS [PY][PX][4] fp16
+//      (channel slots CIN..3 zero: any CIN <= 4 is the same MFMA shape)
+//   2. conv A on the MFMA: M = TAY*TAX A-pixels (16 per tile), N = CA, K = 9 taps x 4 slots (two 16x16x32
+//      steps; weights read as k = tap*CIN + ci), operands gathered from the patch; + bias + act, zeroed
 //      outside the image (conv B's zero padding), -> LDS [A-pixel][CA] with an 80-byte pitch
 //      (conflict-free ds_read_b128 for conv B's stride-2 access)
 //   3. conv B on the MFMA: M = TBY*TBX, N = CB, K = 9 taps x CA; each wave owns 16 output channels and
@@ -27,8 +29,24 @@ namespace {
 
 constexpr int NT = 256;
 
-template <typename S, int CA, int CB, int SA, int TBY, int TBX, int ACT_A, int ACT_B>
+// The image a kernel reads, as its first template argument: the element type itself (_Float16 / float) for the
+// three-plane image — those instantiations keep the names they had before other channel counts existed, which
+// the dispatch goldens and profiles are keyed by — or Planes<element type, CIN> for CIN = 1, 2, 4.
+template <typename S, int CIN> struct Planes {};
+template <typename SRC> struct Image {
+  using type = SRC;
+  static constexpr int cin = 3;
+};
+template <typename S, int CIN> struct Image<Planes<S, CIN>> {
+  using type = S;
+  static constexpr int cin = CIN;
+  static_assert(CIN >= 1 && CIN <= 4 && CIN != 3, "the patch holds four channel slots per pixel; 3 is the plain form");
+};
+
+template <typename SRC, int CA, int CB, int SA, int TBY, int TBX, int ACT_A, int ACT_B>
 __global__ __launch_bounds__(NT, 2) void stem_kernel(const StemParams p) {
+  using S = typename Image<SRC>::type;
+  constexpr int CIN = Image<SRC>::cin;
   constexpr int TAY = 2 * TBY + 1, TAX = 2 * TBX + 1;      // conv-A pixels feeding the tile
   constexpr int PY = SA * (TAY - 1) + 3, PX = SA * (TAX - 1) + 3;
   constexpr int NA = TAY * TAX;
@@ -68,27 +86,37 @@ __global__ __launch_bounds__(NT, 2) void stem_kernel(const StemParams p) {
     wfr[tap] = *reinterpret_cast<const u4*>(reinterpret_cast<const _Float16*>(p.wb) +
                                             (size_t)(wave * 16 + li) * p.kpad_b + tap * CA + g * 8);
 
-  // 1. image patch (PY x PX x 3, zero outside the image): the NEXT tile's pixels are loaded into
-  //    registers while the current tile computes, and written to LDS (fp16, channel 3 zero) at the
+  // 1. image patch (PY x PX x CIN, zero outside the image): the NEXT tile's pixels are loaded into
+  //    registers while the current tile computes, and written to LDS (fp16, channels CIN..3 zero) at the
   //    top of the next iteration, so the image loads' latency sits under conv A / conv B.
   constexpr int PPT = (PY * PX + NT - 1) / NT;   // patch pixels per thread
-  S pre[PPT][3];
+  S pre[PPT][CIN];
   auto prefetch = [&](int t) {
     int tb, ty, tx;
     tile_geom(t, tb, ty, tx);
     const int iy0 = SA * (2 * ty - 1) - 1, ix0 = SA * (2 * tx - 1) - 1;
-    const S* xb = reinterpret_cast<const S*>(p.x) + (size_t)tb * 3 * p.H * p.W;
+    const S* xb = reinterpret_cast<const S*>(p.x) + (size_t)tb * CIN * p.H * p.W;
 #pragma unroll
     for (int k = 0; k < PPT; ++k) {
       const int i = tid + k * NT;
       const int py = i / PX, px = i - py * PX;
       const int iy = iy0 + py, ix = ix0 + px;
-      pre[k][0] = pre[k][1] = pre[k][2] = (S)0.f;
-      if (i < PY * PX && (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W && p.variant != 2) {
-        const size_t o = (size_t)iy * p.W + ix;
-        pre[k][0] = xb[o];
-        pre[k][1] = xb[o + (size_t)p.H * p.W];
-        pre[k][2] = xb[o + 2 * (size_t)p.H * p.W];
+      if constexpr (CIN == 3) {   // (spelled out: these statements compile to the instructions the tuned kernel had)
+        pre[k][0] = pre[k][1] = pre[k][2] = (S)0.f;
+        if (i < PY * PX && (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W && p.variant != 2) {
+          const size_t o = (size_t)iy * p.W + ix;
+          pre[k][0] = xb[o];
+          pre[k][1] = xb[o + (size_t)p.H * p.W];
+          pre[k][2] = xb[o + 2 * (size_t)p.H * p.W];
+        }
+      } else {
+#pragma unroll
+        for (int ch = 0; ch < CIN; ++ch) pre[k][ch] = (S)0.f;
+        if (i < PY * PX && (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W && p.variant != 2) {
+          const size_t o = (size_t)iy * p.W + ix;
+#pragma unroll
+          for (int ch = 0; ch < CIN; ++ch) pre[k][ch] = xb[o + ch * (size_t)p.H * p.W];
+        }
       }
     }
   };
@@ -97,12 +125,12 @@ __global__ __launch_bounds__(NT, 2) void stem_kernel(const StemParams p) {
     for (int k = 0; k < PPT; ++k) {
       const int i = tid + k * NT;
       typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-      const h4 v = {(_Float16)(float)pre[k][0], (_Float16)(float)pre[k][1], (_Float16)(float)pre[k][2],
-                    (_Float16)0.f};
+      auto slot = [&](int ch) { return ch < CIN ? (_Float16)(float)pre[k][ch < CIN ? ch : 0] : (_Float16)0.f; };
+      const h4 v = {slot(0), slot(1), slot(2), slot(3)};
       if (i < PY * PX) *reinterpret_cast<h4*>(patch + i * 4) = v;
     }
   };
-  // conv A's K layout on the MFMA: 4 halves per tap (3 channels + the patch's zero 4th channel),
+  // conv A's K layout on the MFMA: 4 halves per tap (CIN channels + the patch's zero slots),
   // two taps per 8-half lane group, so a lane's A fragment is two 8-byte patch pixels — for the
   // horizontally adjacent pairs one contiguous 16 bytes — instead of eight scattered halves.
   //   K step 0: g0 taps (0,0)(0,1), g1 (1,0)(1,1), g2 (2,0)(2,1), g3 (0,2)(1,2);  K step 1: g0 (2,2).
@@ -133,7 +161,7 @@ __global__ __launch_bounds__(NT, 2) void stem_kernel(const StemParams p) {
         const int tap = tap_of(ks, g, h2);
 #pragma unroll
         for (int ci = 0; ci < 4; ++ci)
-          w8[h2 * 4 + ci] = (tap >= 0 && ci < 3) ? (_Float16)((float)wrow[tap * 3 + ci] * sa_scale) : (_Float16)0.f;
+          w8[h2 * 4 + ci] = (tap >= 0 && ci < CIN) ? (_Float16)((float)wrow[tap * CIN + ci] * sa_scale) : (_Float16)0.f;
       }
       wa[ks][nt] = __builtin_bit_cast(u4, w8);
     }
@@ -277,8 +305,10 @@ __global__ __launch_bounds__(NT, 2) void stem_kernel(const StemParams p) {
 //   * the output staging tile has its own LDS (patch + A tile + staging = 68.6 KB, two blocks per CU),
 //     so a tile needs 3 barriers: [stores of t-1, patch of t] | conv A | conv B + staging;
 //   * both biases in registers from kernel entry (no global load inside the tile loop).
-template <typename S, int CA, int CB, int SA, int TBY, int TBX, int ACT_A, int ACT_B>
+template <typename SRC, int CA, int CB, int SA, int TBY, int TBX, int ACT_A, int ACT_B>
 __global__ __launch_bounds__(NT, 2) void stem2_kernel(const StemParams p) {
+  using S = typename Image<SRC>::type;
+  constexpr int CIN = Image<SRC>::cin;
   constexpr int TAY = 2 * TBY + 1, TAX = 2 * TBX + 1;
   constexpr int PY = SA * (TAY - 1) + 3, PX = SA * (TAX - 1) + 3;
   constexpr int NA = TAY * TAX;
@@ -335,11 +365,11 @@ __global__ __launch_bounds__(NT, 2) void stem2_kernel(const StemParams p) {
   constexpr bool PAIRS = sizeof(S) == 2;
   constexpr int UPR = PAIRS ? (PX + 1) / 2 : PX;        // load units per patch row
   constexpr int PPT = (PY * UPR + NT - 1) / NT;
-  uint32_t pre[PPT][3];
+  uint32_t pre[PPT][CIN];
   // unconditional buffer loads (outside the image: an offset past the buffer reads zero), so no branch
   // hides them from the compiler's wait counting
   const uint32_t plane = (uint32_t)(p.H * p.W * sizeof(S));
-  const auto xr = make_rsrc(p.x, (uint32_t)((size_t)p.B * 3 * plane));
+  const auto xr = make_rsrc(p.x, (uint32_t)((size_t)p.B * CIN * plane));
   // per-thread unit geometry, fixed across tiles
   int u_py[PPT], u_px[PPT];
 #pragma unroll
@@ -352,7 +382,7 @@ __global__ __launch_bounds__(NT, 2) void stem2_kernel(const StemParams p) {
     int tb, ty, tx;
     tile_geom(t, tb, ty, tx);
     const int iy0 = SA * (2 * ty - 1) - 1, ix0 = SA * (2 * tx - 1) - 1;
-    const uint32_t img = (uint32_t)tb * 3u * plane;
+    const uint32_t img = (uint32_t)tb * (uint32_t)CIN * plane;
 #pragma unroll
     for (int k = 0; k < PPT; ++k) {
       const int iy = iy0 + u_py[k], ix = ix0 + u_px[k];
@@ -361,7 +391,7 @@ __global__ __launch_bounds__(NT, 2) void stem2_kernel(const StemParams p) {
       // half, stalling the prefetch on its own loads)
       const uint32_t o = in ? img + (__umul24(iy, p.W) + ix) * (uint32_t)sizeof(S) : 0x80000000u;
 #pragma unroll
-      for (int ch = 0; ch < 3; ++ch) pre[k][ch] = __builtin_amdgcn_raw_buffer_load_b32(xr, o + ch * plane, 0, 0);
+      for (int ch = 0; ch < CIN; ++ch) pre[k][ch] = __builtin_amdgcn_raw_buffer_load_b32(xr, o + ch * plane, 0, 0);
     }
   };
   auto commit = [&]() {
@@ -370,19 +400,26 @@ __global__ __launch_bounds__(NT, 2) void stem2_kernel(const StemParams p) {
     for (int k = 0; k < PPT; ++k) {
       const int i = tid + k * NT;
 #pragma unroll
-      for (int ch = 0; ch < 3; ++ch) asm volatile("" : "+v"(pre[k][ch]));
-      if constexpr (PAIRS) {
+      for (int ch = 0; ch < CIN; ++ch) asm volatile("" : "+v"(pre[k][ch]));
+      if constexpr (PAIRS) {   // a dword = the channel's two pixels; slots CIN..3 zero
         typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-        const h2 c0 = __builtin_bit_cast(h2, pre[k][0]), c1 = __builtin_bit_cast(h2, pre[k][1]),
-                 c2 = __builtin_bit_cast(h2, pre[k][2]);
+        h4 v0, v1;
+#pragma unroll
+        for (int ch = 0; ch < 4; ++ch) {
+          const h2 c = __builtin_bit_cast(h2, ch < CIN ? pre[k][ch < CIN ? ch : 0] : 0u);
+          v0[ch] = c[0];
+          v1[ch] = c[1];
+        }
         const int py = i / UPR, px = 2 * (i - py * UPR);
         if (i < PY * UPR) {
-          *reinterpret_cast<h4*>(patch + (py * PX + px) * 4) = h4{c0[0], c1[0], c2[0], (_Float16)0.f};
-          if (px + 1 < PX) *reinterpret_cast<h4*>(patch + (py * PX + px + 1) * 4) = h4{c0[1], c1[1], c2[1], (_Float16)0.f};
+          *reinterpret_cast<h4*>(patch + (py * PX + px) * 4) = v0;
+          if (px + 1 < PX) *reinterpret_cast<h4*>(patch + (py * PX + px + 1) * 4) = v1;
         }
       } else {
-        const h4 v = {(_Float16)__builtin_bit_cast(float, pre[k][0]), (_Float16)__builtin_bit_cast(float, pre[k][1]),
-                      (_Float16)__builtin_bit_cast(float, pre[k][2]), (_Float16)0.f};
+        h4 v;
+#pragma unroll
+        for (int ch = 0; ch < 4; ++ch)
+          v[ch] = ch < CIN ? (_Float16)__builtin_bit_cast(float, pre[k][ch < CIN ? ch : 0]) : (_Float16)0.f;
         if (i < PY * PX) *reinterpret_cast<h4*>(patch + i * 4) = v;
       }
     }
@@ -409,9 +446,8 @@ __global__ __launch_bounds__(NT, 2) void stem2_kernel(const StemParams p) {
       for (int h2 = 0; h2 < 2; ++h2) {
         const int tap = tap_of(ks, g, h2);
 #pragma unroll
-        for (int ci = 0; ci < 3; ++ci)
-          w8[h2 * 4 + ci] = tap >= 0 ? (_Float16)((float)wrow[tap * 3 + ci] * sa_scale) : (_Float16)0.f;
-        w8[h2 * 4 + 3] = (_Float16)0.f;
+        for (int ci = 0; ci < 4; ++ci)
+          w8[h2 * 4 + ci] = (tap >= 0 && ci < CIN) ? (_Float16)((float)wrow[tap * CIN + ci] * sa_scale) : (_Float16)0.f;
       }
       wa[ks][nt] = __builtin_bit_cast(u4, w8);
     }
@@ -914,36 +950,48 @@ hipError_t stem_reorg_acts(const StemParams& p, hipStream_t st) {
   return launch_with_act(p.act_a, [&](auto A) { return stem_reorg_t<S, decltype(A)::value, decltype(A)::value>(p, st); });
 }
 
-template <typename S, int CA, int CB, int SA, int ACT_A, int ACT_B>
+template <int CIN, typename S, int CA, int CB, int SA, int ACT_A, int ACT_B>
 hipError_t stem_t(const StemParams& p, hipStream_t st) {
+  using SRC = std::conditional_t<CIN == 3, S, Planes<S, CIN>>;
   constexpr int TBY = 8, TBX = 16;
   const int HB = p.H / SA / 2, WB = p.W / SA / 2;
   const int ntiles = p.B * ((HB + TBY - 1) / TBY) * ((WB + TBX - 1) / TBX);
   const int cus = device_cus();
   static const int occ = env_int("YV7_STEM_OCC", 2);
   const int nblk = ntiles < cus * occ ? ntiles : cus * occ;   // persistent: blocks walk the tiles
-  static const int form = env_int("YV7_STEM", 2);
   if constexpr (SA == 1) {   // (SA = 2, yolov7-tiny: its 10 patch pixels per thread leave stem2 one block per CU)
+    // YV7_STEM=1, the first form: kept for the three-plane image only (the other counts build each stride's
+    // default form)
+    static const int form = CIN == 3 ? env_int("YV7_STEM", 2) : 2;
     if (form != 1) {
-      YV7_LAUNCH((stem2_kernel<S, CA, CB, SA, TBY, TBX, ACT_A, ACT_B>), dim3(nblk), dim3(NT), 0, st, p);
+      YV7_LAUNCH((stem2_kernel<SRC, CA, CB, SA, TBY, TBX, ACT_A, ACT_B>), dim3(nblk), dim3(NT), 0, st, p);
       return hipGetLastError();
     }
   }
-  YV7_LAUNCH((stem_kernel<S, CA, CB, SA, TBY, TBX, ACT_A, ACT_B>), dim3(nblk), dim3(NT), 0, st, p);
+  if constexpr (SA == 1 && CIN != 3) return hipErrorInvalidValue;   // (not reached: form is 2)
+  else YV7_LAUNCH((stem_kernel<SRC, CA, CB, SA, TBY, TBX, ACT_A, ACT_B>), dim3(nblk), dim3(NT), 0, st, p);
   return hipGetLastError();
 }
 
-template <typename S, int CA, int CB, int SA>
+template <int CIN, typename S, int CA, int CB, int SA>
 hipError_t stem_acts(const StemParams& p, hipStream_t st) {
   // mixed activations: not a stem the graph compiler emits
   if (p.act_a != p.act_b || p.act_a < 0 || p.act_a > 2) return hipErrorInvalidValue;
-  return launch_with_act(p.act_a, [&](auto A) { return stem_t<S, CA, CB, SA, decltype(A)::value, decltype(A)::value>(p, st); });
+  return launch_with_act(p.act_a, [&](auto A) { return stem_t<CIN, S, CA, CB, SA, decltype(A)::value, decltype(A)::value>(p, st); });
+}
+
+template <int CIN>
+hipError_t stem_cin(const StemParams& p, int x_dtype, hipStream_t st) {
+  if (p.sa == 1)
+    return x_dtype == 1 ? stem_acts<CIN, _Float16, 32, 64, 1>(p, st) : stem_acts<CIN, float, 32, 64, 1>(p, st);
+  return x_dtype == 1 ? stem_acts<CIN, _Float16, 32, 64, 2>(p, st) : stem_acts<CIN, float, 32, 64, 2>(p, st);
 }
 
 }  // namespace
 
 bool stem_supported(int cin, int ca, int cb, int sa) {
-  return (cin == 3 && ca == 32 && cb == 64 && (sa == 1 || sa == 2)) || (cin == 12 && ca == 64 && cb == 128 && sa == 1);
+  return (cin >= 1 && cin <= 4 && ca == 32 && cb == 64 && (sa == 1 || sa == 2)) ||
+         (cin == 12 && ca == 64 && cb == 128 && sa == 1);
 }
 
 hipError_t launch_stem(const StemParams& p, int x_dtype, hipStream_t st) {
@@ -951,9 +999,13 @@ hipError_t launch_stem(const StemParams& p, int x_dtype, hipStream_t st) {
     if (p.H % 4 || p.W % 4) return hipErrorInvalidValue;
     return x_dtype == 1 ? stem_reorg_acts<_Float16>(p, st) : stem_reorg_acts<float>(p, st);
   }
-  if (p.sa == 1)
-    return x_dtype == 1 ? stem_acts<_Float16, 32, 64, 1>(p, st) : stem_acts<float, 32, 64, 1>(p, st);
-  return x_dtype == 1 ? stem_acts<_Float16, 32, 64, 2>(p, st) : stem_acts<float, 32, 64, 2>(p, st);
+  switch (p.cin) {   // the image's channel count (Model(cfg, ch=C))
+    case 1: return stem_cin<1>(p, x_dtype, st);
+    case 2: return stem_cin<2>(p, x_dtype, st);
+    case 3: return stem_cin<3>(p, x_dtype, st);
+    case 4: return stem_cin<4>(p, x_dtype, st);
+    default: return hipErrorInvalidValue;
+  }
 }
 
 }  // namespace yv7

@@ -256,15 +256,16 @@ hipError_t launch_conv_f8(const F8ConvParams& p, hipStream_t st);
 
 // Fused stem: image -> conv A (3 -> 32, 3x3, stride sa) -> conv B (32 -> 64, 3x3, stride 2).
 struct StemParams {
-  const void* x;        // [B,3,H,W] image (fp16 or fp32)
+  const void* x;        // [B,cin,H,W] image (fp16 or fp32); the w6 front end: [B,3,H,W]
   void* y;              // conv-B output tensor (bordered NHWC fp16)
-  const void* wa;       // conv-A weights [32][kpad_a] (k = tap*3 + ci)
+  const void* wa;       // conv-A weights [32][kpad_a] (k = tap*cin + ci)
   const float* ba;
   const void* wb;       // conv-B weights [64][kpad_b] (k = tap*32 + ci)
   const float* bb;
   int B, H, W, yc, yoff, kpad_a, kpad_b, act_a, act_b, sa;
   int variant;          // 0; >0: microbenchmark hooks (scripts/stembench.hip)
   int reorg;            // 1: the w6 front end (ReOrg + 12 -> 64 -> 128, wa k = tap*16 + ci), stem_reorg_kernel
+  int cin;              // conv A's input channels: the image's 1..4 planes (reorg: 12, three image planes)
 };
 
 // Host launchers (defined in the .hip files, called from the runtime), by the file that defines them.
@@ -314,7 +315,8 @@ hipError_t launch_conv_s2(const ConvParams& p, int cfg, hipStream_t st);
 bool w1_supported(const ConvParams& p, int cfg);
 hipError_t launch_conv_w1(const ConvParams& p, int cfg, hipStream_t st);
 // elementwise.hip / stem.hip
-hipError_t launch_input(int dtype, const void* x, int x_dtype, void* y, int B, int H, int W, int yc,
+// x [B,C,H,W] -> y's first C (reorg: 4 C) channels of yc, the rest zero
+hipError_t launch_input(int dtype, const void* x, int x_dtype, void* y, int B, int C, int H, int W, int yc,
                         bool reorg, hipStream_t st);
 hipError_t launch_maxpool(int dtype, const void* x, int B, int H, int W, int xc, int xoff, void* y, int Ho,
                           int Wo, int yc, int yoff, int C, int k, int s, int pad, hipStream_t st);

@@ -30,7 +30,7 @@ import torch  # noqa: E402
 from models.experimental import attempt_load  # noqa: E402
 from utils.datasets import (OUT_F16_CHW, OUT_F32_CHW, LoadImages, imread, letterbox_geometry,  # noqa: E402
                             letterbox_ragged)
-from utils.general import (check_img_size, nms_batched, non_max_suppression, scale_boxes, scale_coords,  # noqa: E402
+from utils.general import (check_img_size, check_three_channels, nms_batched, non_max_suppression, scale_boxes, scale_coords,  # noqa: E402
                            scale_desc, xyxy2xywh)
 from utils.plots import color_list, plot_boxes  # noqa: E402
 from utils.torch_utils import select_device, time_synchronized  # noqa: E402
@@ -114,6 +114,7 @@ def detect(opt):
         raise RuntimeError('detect.py: the MI355X path has no CPU execution (oracle/ holds the CPU reference)')
     half = not opt.fp32                                   # detect.py:38 (half on every GPU device)
     model = load_model(opt, device)
+    check_three_channels(model)
     stride = int(model.stride.max())
     imgsz = check_img_size(opt.img_size, s=stride)
     if half:

@@ -27,7 +27,7 @@ import torch
 import torch.nn as nn
 
 from utils.datasets import OUT_F16_CHW, OUT_F32_CHW, autoshape_geometry, letterbox_ragged
-from utils.general import increment_path, nms_batched, non_max_suppression, scale_boxes, xyxy2xywh
+from utils.general import check_three_channels, increment_path, nms_batched, non_max_suppression, scale_boxes, xyxy2xywh
 from utils.plots import color_list, plot_boxes
 from utils.torch_utils import fuse_conv_and_bn, time_synchronized
 
@@ -252,6 +252,7 @@ class autoShape(nn.Module):  # common.py:865-932
 
     def __init__(self, model):
         super().__init__()
+        check_three_channels(model)
         self.model = model.eval()
 
     def autoshape(self):

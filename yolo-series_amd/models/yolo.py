@@ -320,7 +320,7 @@ class Model(nn.Module):
 
     def fp8(self, calib=None):
         """BASELINE configs[4]: half() with the 1x1 convs on OCP e4m3 weights and activations (the
-        block-scaled fp8 MFMA); `calib`: [B,3,H,W] frames in [0,1] that set the activation scales
+        block-scaled fp8 MFMA); `calib`: [B,C,H,W] frames in [0,1] that set the activation scales
         (default: seeded synthetic frames) — yv7.runtime.Plan.fp8_from_model.  .float() leaves it."""
         self.half()
         self._fp8 = (calib,)

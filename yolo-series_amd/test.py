@@ -50,7 +50,7 @@ import torch  # noqa: E402
 
 from models.experimental import attempt_load  # noqa: E402
 from utils.datasets import ValLoader, create_dataloader  # noqa: E402
-from utils.general import (check_dataset, check_file, check_img_size, coco80_to_coco91_class,  # noqa: E402
+from utils.general import (check_dataset, check_file, check_img_size, check_three_channels, coco80_to_coco91_class,  # noqa: E402
                            increment_path, nms_batched, scale_boxes, xyxy2xywh)
 from utils.metrics import ConfusionMatrix, ap_per_class, match_batch  # noqa: E402
 from utils.plots import mosaic_tables, plot_images  # noqa: E402
@@ -146,6 +146,7 @@ def test(data,
         save_dir = Path(increment_path(Path(opt.project) / opt.name, exist_ok=opt.exist_ok))
         (save_dir / 'labels' if save_txt else save_dir).mkdir(parents=True, exist_ok=True)
         model = load_model(weights, device)
+        check_three_channels(model)   # (the loader below is this function's own)
         gs = max(int(model.stride.max()), 32)
         imgsz = check_img_size(imgsz, s=gs)
     elif save_txt:

@@ -35,6 +35,15 @@ def check_img_size(img_size, s=32):  # general.py:124-129
     return new_size
 
 
+def check_three_channels(model):
+    """For the entry points that load images themselves (autoShape, detect.py, test.py's loader), which produce
+    3-channel frames as the reference's loaders do: a model built with another channel count (Model(cfg, ch=C),
+    a single model or an Ensemble) is refused here, before any forward."""
+    for m in (model if isinstance(model, torch.nn.ModuleList) else [model]):
+        if getattr(m, 'yaml', {}).get('ch', 3) != 3:
+            raise RuntimeError('this entry point loads 3-channel images; call the model on a [B,C,H,W] tensor')
+
+
 def check_file(file):  # general.py:146-154
     if file == '' or Path(file).is_file():
         return file

@@ -67,7 +67,7 @@ def fuse_conv_and_bn(conv, bn):
 
 
 def scale_img(img, ratio=1.0, same_shape=False, gs=32):
-    """Resize a [B,3,H,W] batch by ratio and pad to a gs multiple with 0.447 (TTA helper)."""
+    """Resize a [B,C,H,W] batch by ratio and pad to a gs multiple with 0.447 (TTA helper)."""
     if ratio == 1.0:
         return img
     h, w = img.shape[2:]

@@ -18,6 +18,8 @@ kernel launch:
                               fp16 plans of the w6 front end: ReOrg + its two convs as one STEM op
   Detect / IDetect / IAuxDetect -> one DETECT op per level (1x1 conv + bias + sigmoid + decode -> z)
 Layers whose outputs never reach the head (IAuxDetect's auxiliary branch) are not emitted.
+The image's channel count C is the model's (Model(cfg, ch=C), model.yaml['ch']): Graph.in_channels; the INPUT op
+packs C (behind a ReOrg 4 C) channels, the fused 32 / 64 stem takes C <= 4 (_STEMS).
 
 compile_model is the driver: layer shapes (_shapes), the front end (_front_end: INPUT op or fused STEM), concat
 placement (_place_concats), one emitter per layer kind (_EMITTERS) over a shared _Lowering, then the op-list
@@ -53,6 +55,7 @@ class Graph:
     stride: list = None
     anchor_grid: list = None
     max_shift: int = 0
+    in_channels: int = 3                               # C of the [B,C,H,W] image (Model(cfg, ch=C))
     layer_tensor: dict = field(default_factory=dict)   # layer i -> (tensor, coff, channels) for debugging
     flops_per_pixel: float = 0.0                       # conv MACs*2 per input pixel (for roofline accounting)
 
@@ -232,10 +235,12 @@ def _shapes(layers, c_in):
 
 # The front ends that run as one fused fp16 STEM op (csrc/stem.hip) straight from the image: [ReOrg ->] conv A
 # (3x3, pad 1) -> conv B (3x3, stride 2, pad 1), every layer before B read only by its successor.  Per row:
-# leading ReOrg; A's cin, cout, strides; B's cout; A's K pad per tap (the w6 row reads the 12-channel
-# space-to-depth image with K = tap * 16 + ci)
-_STEMS = ((False, 3, 32, (1, 2), 64, 3),  # yolov7 / yolov7-tiny, layers 0-1
-          (True, 12, 64, (1,), 128, 16))  # yolov7-w6, layers 0-2 (cfg/deploy/yolov7-w6.yaml:14-16, stem_reorg_kernel)
+# leading ReOrg; A's cin (the image's channels C where there is no ReOrg: Model(cfg, ch=C), any count the patch's
+# four channel slots hold), cout, strides; B's cout; A's K pad per tap (None: cin itself, K = tap * C + ci; the w6
+# row reads the 12-channel space-to-depth image with K = tap * 16 + ci).  Whatever matches no row (a ReOrg model
+# with C != 3, any model with C > 4) lowers to INPUT + CONV ops.
+_STEMS = ((False, (1, 2, 3, 4), 32, (1, 2), 64, None),  # yolov7 / yolov7-tiny, layers 0-1
+          (True, (12,), 64, (1,), 128, 16))  # yolov7-w6, layers 0-2 (cfg/deploy/yolov7-w6.yaml:14-16, stem_reorg_kernel)
 _Stem = namedtuple('_Stem', 'at cin kpad')   # the layer that carries the op (layers before it are folded into it)
 
 
@@ -243,7 +248,7 @@ def _stem_candidate(layers, dtype):
     """The row of _STEMS the first layers match, as a _Stem, or None (fp16 plans only)."""
     if dtype != L.DT_F16:
         return None
-    for reorg, cin, cout, strides, cout2, kpad in _STEMS:
+    for reorg, cins, cout, strides, cout2, kpad in _STEMS:
         at = 2 if reorg else 1
         if len(layers) < at + 2 or isinstance(layers[0], ReOrg) != reorg:
             continue
@@ -251,13 +256,13 @@ def _stem_candidate(layers, dtype):
         if not (type(la) is Conv and type(lb) is Conv and all(m.f == -1 for m in layers[1:at + 1])):
             continue
         a, b = la.conv, lb.conv
-        if not (a.in_channels == cin and a.out_channels == cout and a.kernel_size[0] == 3 and a.stride[0] in strides
+        if not (a.in_channels in cins and a.out_channels == cout and a.kernel_size[0] == 3 and a.stride[0] in strides
                 and a.padding[0] == 1 and b.out_channels == cout2 and b.kernel_size[0] == 3 and b.stride[0] == 2
                 and b.padding[0] == 1 and a.groups == 1 and b.groups == 1 and _act_code(la.act) == _act_code(lb.act)):
             continue
         if any(j < at for m in layers[at + 1:] for j in _sources(m) if j >= 0):
             continue
-        return _Stem(at, cin, kpad)
+        return _Stem(at, a.in_channels, kpad or a.in_channels)
     return None
 
 
@@ -305,9 +310,10 @@ class _Lowering:
 
 def _front_end(g: Graph, layers, V, ch, shift, stem):
     """Tensor 0, the packed network input: written by the INPUT op (a ReOrg at layer 0 is fused into it), or an
-    unused placeholder where the fused stem reads the image itself."""
+    unused placeholder where the fused stem reads the image itself.  The INPUT op's cout is what the C side packs:
+    the image's C channels, 4 C behind a ReOrg."""
     reorg0 = isinstance(layers[0], ReOrg)
-    in_c = 12 if reorg0 else 3
+    in_c = 4 * ch[-1] if reorg0 else ch[-1]
     if stem is not None:
         return _Lowering(g, V, ch, shift, g.add_tensor(V, g.max_shift), in_c)
     cx = _Lowering(g, V, ch, shift, g.add_tensor(_rup(in_c, V), 1 if reorg0 else 0), in_c)
@@ -447,8 +453,7 @@ def compile_model(model, dtype: int, fp8=None) -> Graph:
     live = _live_layers(layers, det.nl)
     ch, shift = _shapes(layers, model.yaml.get('ch', 3))
     g.max_shift = max(shift.values())
-    if ch[-1] != 3:
-        raise NotImplementedError('the input packing op handles 3-channel images')
+    g.in_channels = ch[-1]
 
     stem = None if no_stem else _stem_candidate(layers, dtype)
     cx = _front_end(g, layers, _vec(dtype), ch, shift, stem)

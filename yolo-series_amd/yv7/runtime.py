@@ -100,6 +100,7 @@ class Plan:
         self.device = torch.device(device)
         self.dtype = graph.dtype
         self.nl, self.na, self.no = graph.nl, graph.na, graph.no
+        self.in_channels = graph.in_channels   # C of the [B,C,H,W] batches the plan takes (Model(cfg, ch=C))
         lib = L.lib()
         self._tensors = (L.TensorDesc * len(graph.tensors))(*[L.TensorDesc(c, s) for c, s in graph.tensors])
         ops = op_descs(graph)
@@ -143,7 +144,7 @@ class Plan:
     @classmethod
     def fp8_scales(cls, model, device, calib=None, min_cout=None):
         """{op index: activation scale} of the fp8 plan's e4m3 convs, from calibration: the fp16 plan runs
-        `calib` ([B,3,H,W] frames in [0,1]; default: 2 seeded synthetic frames at the model's native size)
+        `calib` ([B,C,H,W] frames in [0,1]; default: 2 seeded synthetic frames at the model's native size)
         and each fp8 op's input amax sets xscale = 2**ceil(log2(amax / 448)), so the largest calibrated
         value still fits e4m3.  min_cout: which eligible 1x1 convs go fp8 (default
         yv7.graph.FP8_MIN_COUT; 0 = all of them)."""
@@ -153,7 +154,7 @@ class Plan:
         if calib is None:
             from yv7.synthetic import synthetic_frames
             hw = 1280 if float(model.stride.max()) >= 64 else 640
-            calib = synthetic_frames(2, hw, hw, seed=4321)
+            calib = synthetic_frames(2, hw, hw, seed=4321, ch=base.in_channels)
         x = calib.to(base.device).half()
         B, _, H, W = x.shape
         N = base.num_rows(H, W)
@@ -182,7 +183,7 @@ class Plan:
         return int(L.lib().yv7_num_rows(self._h, H, W))
 
     def workspace(self, B, H, W, slot=0):
-        """The forward workspace for a [B,3,H,W] batch; `slot` > 0 gives further ones, so that
+        """The forward workspace for a [B,C,H,W] batch; `slot` > 0 gives further ones, so that
         sub-batches can run concurrently on their own streams."""
         key = (B, H, W, slot)
         ws = self._ws.get(key)
@@ -250,7 +251,7 @@ class Plan:
 
     def op_kernels(self, B, H, W, x_dtype=None):
         """Per op, the kernel names (rocprofv3's demangled symbols) the dispatch launches for a
-        [B,3,H,W] forward (yv7_op_kernels: a dry run, nothing executes); [] for an op without a
+        [B,C,H,W] forward (yv7_op_kernels: a dry run, nothing executes); [] for an op without a
         kernel of its own (the later pools of the SPPCSPC cascade)."""
         buf = ctypes.create_string_buffer(1 << 20)
         with torch.cuda.device(self.device):
@@ -263,12 +264,13 @@ class Plan:
         return out
 
     def op_costs(self, B, H, W, x_bytes=4, with_raw=True):
-        """Per op: (kind, algorithmic FLOPs, algorithmic HBM bytes) for a [B,3,H,W] batch.
+        """Per op: (kind, algorithmic FLOPs, algorithmic HBM bytes) for a [B,C,H,W] batch.
 
         Bytes follow the layer-boundary model: every op reads its input slice once and
         writes its output once, weights once per batch; concat costs nothing; the head writes z in
         fp32 (and the raw logits, also fp32, which the reference returns as xs)."""
         es = 2 if self.dtype == L.DT_F16 else 4
+        C = self.graph.in_channels
         out = []
         for o in self.graph.ops:
             kind = o['kind']
@@ -280,13 +282,13 @@ class Plan:
                 ca, cb = o['cout'], o['cout2']
                 flops = 2.0 * B * Ha * Wa * ca * 9 * cin + 2.0 * B * (Ha // 2) * (Wa // 2) * cb * 9 * ca
                 # reference-boundary bytes of the two layers it replaces (input read, A write + read, B write)
-                by = B * 3 * H * W * x_bytes + 2 * B * Ha * Wa * ca * es + B * (Ha // 2) * (Wa // 2) * cb * es
+                by = B * C * H * W * x_bytes + 2 * B * Ha * Wa * ca * es + B * (Ha // 2) * (Wa // 2) * cb * es
                 out.append((kind, flops, by))
                 continue
             if kind == L.OP_INPUT:
                 sh = self.graph.tensors[o['dst']][1]
                 npx = B * (H >> sh) * (W >> sh)
-                out.append((kind, 0.0, B * 3 * H * W * x_bytes + npx * self.graph.tensors[o['dst']][0] * es))
+                out.append((kind, 0.0, B * C * H * W * x_bytes + npx * self.graph.tensors[o['dst']][0] * es))
                 continue
             si = self.graph.tensors[o['src']][1]
             Hi, Wi = H >> si, W >> si
@@ -320,9 +322,10 @@ class Plan:
         """Forward into caller buffers; rowbest (optional): [B, N, 4] 32-bit yv7_row_best records.
         stream: a torch.cuda.Stream (default: the current stream); on a side stream every buffer the
         forward touches is recorded on it, so the allocator cannot reuse it before the forward is done."""
-        B, C, H, W = x.shape
-        if C != 3:
-            raise ValueError(f'expected a [B,3,H,W] image batch, got {tuple(x.shape)}')
+        if x.dim() != 4 or x.shape[1] != self.in_channels:
+            raise ValueError(f'expected a [B,{self.in_channels},H,W] image batch (the plan was compiled for '
+                             f'{self.in_channels} input channels), got {tuple(x.shape)}')
+        B, _, H, W = x.shape
         if x.dtype not in (torch.float32, torch.float16):
             x = x.float()
         x = x.contiguous()
@@ -342,9 +345,12 @@ class Plan:
         L.check(rc, 'yv7_forward')
 
     def forward(self, x, want_raw=True):
-        """x [B,3,H,W] on the plan's device -> (z [B,N,no] fp32, xs: list of [B,na,ny,nx,no] fp32)."""
+        """x [B,C,H,W] on the plan's device -> (z [B,N,no] fp32, xs: list of [B,na,ny,nx,no] fp32)."""
         if x.device != self.device and not (self.device.index is None and x.is_cuda):
             raise RuntimeError(f'input on {x.device}, plan on {self.device}')
+        if x.dim() != 4 or x.shape[1] != self.in_channels:
+            raise ValueError(f'expected a [B,{self.in_channels},H,W] image batch (the plan was compiled for '
+                             f'{self.in_channels} input channels), got {tuple(x.shape)}')
         B, _, H, W = x.shape
         N = self.num_rows(H, W)
         if N <= 0:
@@ -377,7 +383,7 @@ class Inflight:
     deterministic and no scratch is shared between streams (NMS scratch is per stream).
 
         run = Inflight(plan, B, H, W, streams=3)
-        h = run.submit(x)                 # x [B,3,H,W] on the plan's device, produced on the current stream
+        h = run.submit(x)                 # x [B,C,H,W] on the plan's device, produced on the current stream
         det, src_row, count = run.result(h)   # waits for that batch only; valid until S more submits
 
     post(det, src_row, count) (optional) runs on the batch's stream after its NMS, e.g.
@@ -402,7 +408,7 @@ class Inflight:
         N = plan.num_rows(H, W)
         if N <= 0:
             L.check(-2, f'yv7_num_rows(H={H}, W={W})')
-        self.shape = (B, 3, H, W)
+        self.shape = (B, getattr(plan, 'in_channels', 3), H, W)
         S = self.S
         prios = list(priorities) if priorities is not None else [0] * S   # HIP stream priorities (-1 = high)
         self.streams = [None if self.host else torch.cuda.Stream(dev, priority=prios[i % len(prios)]) for i in range(S)]

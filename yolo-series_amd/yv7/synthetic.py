@@ -10,7 +10,7 @@ the reference's state_dict layout that behave like a trained
     order of 10^3 NMS candidates at conf 0.25 (the reference's _initialize_biases prior alone gives
     sigmoid(obj) ~ 1e-4..1e-2, i.e. no detections — SURVEY §7.2 hard part 7).
 `synthetic_frames(B, H, W, seed)` gives uint8-derived [0,1] frames as the reference's pre-processing
-would (detect.py:100-104).
+would (detect.py:100-104), with ch planes (3 unless the model was built with Model(cfg, ch=C)).
 """
 from __future__ import annotations
 
@@ -94,7 +94,7 @@ def synthetic_state_dict(model, seed=0, head_gain=2.0, target_candidates=0.06, c
     """Fill `model` (unfused) in place with seeded synthetic weights and return its state_dict.
 
     The BatchNorm statistics are estimated layer by layer on one synthetic frame
-    (1 x 3 x calib_hw x calib_hw), the way a training pass accumulates them, and the head biases are
+    (1 x C x calib_hw x calib_hw, C the model's input channels), the way a training pass accumulates them, and the head biases are
     set so that `target_candidates` of the anchor rows pass conf 0.25 on that frame; this is weight
     synthesis only — inference never runs here."""
     gen = _Gen(seed)
@@ -102,7 +102,7 @@ def synthetic_state_dict(model, seed=0, head_gain=2.0, target_candidates=0.06, c
     layers = list(model.model)
     if calib_hw is None:  # the model's native resolution: 640 for P5, 1280 for P6 (max stride 64)
         calib_hw = 1280 if float(model.stride.max()) >= 64 else 640
-    x0 = synthetic_frames(1, calib_hw, calib_hw, seed=seed + 12345)
+    x0 = synthetic_frames(1, calib_hw, calib_hw, seed=seed + 12345, ch=model.yaml.get('ch', 3))
     y = []
     x = x0
     for m in layers:
@@ -179,8 +179,8 @@ def synthetic_state_dict(model, seed=0, head_gain=2.0, target_candidates=0.06, c
     return {k: v.clone() for k, v in model.state_dict().items()}
 
 
-def synthetic_frames(B, H, W, seed=0, device='cpu', dtype=torch.float32):
-    """uint8 frames in [0,255] -> /255 float [B,3,H,W] (the reference's img/255 pre-processing)."""
+def synthetic_frames(B, H, W, seed=0, device='cpu', dtype=torch.float32, ch=3):
+    """uint8 frames in [0,255] -> /255 float [B,ch,H,W] (the reference's img/255 pre-processing)."""
     g = torch.Generator().manual_seed(seed)
-    x = torch.randint(0, 256, (B, 3, H, W), generator=g, dtype=torch.uint8)
+    x = torch.randint(0, 256, (B, ch, H, W), generator=g, dtype=torch.uint8)
     return (x.to(device).to(dtype) / 255.0)
