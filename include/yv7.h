@@ -23,6 +23,8 @@
  *                     conversion                                detect.py:100-104, datasets.py:199
  *   yv7_letterbox_ragged  the same for frames of different    models/common.py:899-918 (autoShape's
  *                     sizes on one canvas                       letterbox loop, np.stack, transpose, / 255)
+ *   yv7_letterbox_c, yv7_letterbox_ragged_c  both for frames of 1..16 channels (no counterpart: the
+ *                     original's loaders are 3-channel)
  *   yv7_scale_boxes   scale_coords() + clip_coords(),           utils/general.py:340-361, detect.py:183,
  *                     .round(), the Detections views            models/common.py:940-948
  *   yv7_match         the per-image, per-class matching of      test.py:123,131,179-213
@@ -245,7 +247,7 @@ int yv7_letterbox(const void* src, int B, int H, int W, int new_h, int new_w, in
  * BGR frames -> RGB planes, detect.py).  The coefficients are computed inline, so the workspace size is 0
  * and workspace may be null. */
 typedef struct {
-  const void* data;                /* device pointer, uint8 [h][w][3], packed rows */
+  const void* data;                /* device pointer, uint8 [h][w][3] ([h][w][channels] for the _c form), packed */
   int32_t h, w;                    /* source size */
   int32_t new_h, new_w, top, left; /* resized size and its place on the canvas */
 } yv7_frame_desc;
@@ -253,6 +255,28 @@ typedef struct {
 size_t yv7_letterbox_ragged_workspace_bytes(const yv7_frame_desc* frames, int B);
 int yv7_letterbox_ragged(const yv7_frame_desc* frames, int B, int out_h, int out_w, int pad0, int pad1, int pad2,
                          int swap_rb, int out_kind, void* dst, void* workspace, size_t ws_bytes, void* stream);
+
+/* Both letterboxes for frames of `channels` interleaved channels, 1..YV7_LETTERBOX_MAX_CH (grayscale, thermal,
+ * RGBA, RGB+IR ...): src is uint8 [B][H][W][channels], yv7_frame_desc::data uint8 [h][w][channels], packed.  Per
+ * frame the arithmetic is yv7_letterbox's with cn = channels: the same identity, exact-2x area and bilinear modes
+ * and coefficients; in the bilinear vertical pass value (x, c) rounds in two steps iff
+ * x * channels + c < new_w * channels / 16 * 16 (the SIMD pass runs over the interleaved row; this is
+ * oracle/letterbox_ref.py resize_linear_u8 on an [h][w][channels] array).  Outside the resized frame channel c
+ * takes pad[c]; pad is a host array of `channels` bytes, read before the call returns.  out_kind 0 writes uint8
+ * [B][out_h][out_w][channels] (dst aligned to one pixel for 2 and 4 channels, which store a pixel at once); 1 and
+ * 2 write fp16 / fp32 [B][channels][out_h][out_w], each value (float)v / 255.0f rounded once, planes in the
+ * input's order.  swap_rb = 1 reverses the float planes and is legal with channels == 3 only; the uint8 kind
+ * ignores it.  With channels == 3, yv7_letterbox_ragged_c equals yv7_letterbox_ragged and
+ * yv7_letterbox_c(swap_rb = 1) equals yv7_letterbox bit for bit (they launch the same kernels).  Workspaces are
+ * the 3-channel functions'.  Asynchronous, no device synchronisation; the ragged form makes no copy either.
+ * YV7_E_ARG: channels out of range, swap_rb with channels != 3, null pad, a misaligned 2- / 4-channel uint8 dst. */
+#define YV7_LETTERBOX_MAX_CH 16
+int yv7_letterbox_c(const void* src, int B, int H, int W, int channels, int new_h, int new_w, int top, int left,
+                    int out_h, int out_w, const uint8_t* pad, int swap_rb, int out_kind, void* dst, void* workspace,
+                    size_t ws_bytes, void* stream);
+int yv7_letterbox_ragged_c(const yv7_frame_desc* frames, int B, int channels, int out_h, int out_w,
+                           const uint8_t* pad, int swap_rb, int out_kind, void* dst, void* workspace,
+                           size_t ws_bytes, void* stream);
 
 /* Boxes back to image pixels (replaces utils/general.py:340-361 scale_coords(ratio_pad=None) + clip_coords,
  * detect.py:183's .round() and the derived views of Detections.__init__, models/common.py:940-948) on yv7_nms's

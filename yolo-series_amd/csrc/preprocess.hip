@@ -144,23 +144,156 @@ __global__ void letterbox_ragged_kernel(LbChunk ch, int b0, int oh, int ow, uint
   }
 }
 
+// ---- any channel count 1..LETTERBOX_MAX_CH (grayscale, thermal, RGBA, RGB+IR frames): packed [H][W][cn] in,
+// uint8 [oh][ow][cn] or float planes [cn][oh][ow] out.  CN is the count at compile time (1..4) or 0 for a
+// run-time count (5..16).  One thread per output pixel as above; the pixel's taps are computed once and every
+// channel's fetches, vertical pass and store sit inside the channel loop, so no per-thread array is indexed by
+// a run-time value.  The pad bytes travel by value in two words, picked by shifts.
+struct LbPad {
+  uint64_t lo, hi;   // channels 0..7 and 8..15, channel c at bits 8 * (c & 7)
+};
+
+__device__ __forceinline__ int lb_pad(const LbPad& p, int c) {
+  return (int)(((c < 8 ? p.lo : p.hi) >> ((c & 7) * 8)) & 255);
+}
+
+// pix: the pixel's index in the uint8 output, o: its offset in plane 0 of its float frame
+template <int OUT, int CN>
+__device__ __forceinline__ void lb_pixel_cn(bool inside, const uint8_t* __restrict__ img, int W, int cn_rt, int mode,
+                                            const ResizeTap& cx, const ResizeTap& cy, int x, int y, int nw,
+                                            const LbPad& pad, void* __restrict__ dst, size_t pix, size_t plane,
+                                            size_t o) {
+  const int cn = CN ? CN : cn_rt;
+  const int nv = resize_split(nw, cn);
+  uint32_t packed = 0;
+#pragma clang loop unroll_count(CN ? CN : 1)
+  for (int c = 0; c < cn; ++c) {
+    const int v = inside ? resize_value_cn(img, W, cn, mode, cx, cy, x, y, c, nv) : lb_pad(pad, c);
+    if constexpr (OUT == 0) {
+      if constexpr (CN == 2 || CN == 4) packed |= (uint32_t)v << (8 * c);
+      else reinterpret_cast<uint8_t*>(dst)[pix * cn + c] = (uint8_t)v;
+    } else {
+      // planes in the input's channel order; x / 255 in float (fp16: rounded once)
+      const float f = (float)v / 255.0f;
+      const size_t at = o + (size_t)c * plane;
+      if constexpr (OUT == 1) reinterpret_cast<_Float16*>(dst)[at] = (_Float16)f;
+      else reinterpret_cast<float*>(dst)[at] = f;
+    }
+  }
+  if constexpr (OUT == 0 && CN == 4) reinterpret_cast<uint32_t*>(dst)[pix] = packed;
+  if constexpr (OUT == 0 && CN == 2) reinterpret_cast<uint16_t*>(dst)[pix] = (uint16_t)packed;
+}
+
+template <int OUT, int CN>
+__global__ void letterbox_cn_kernel(const uint8_t* __restrict__ src, int H, int W, int cn_rt, int nh, int nw, int top,
+                                    int left, int oh, int ow, LbPad pad, int mode, LbTab t,
+                                    void* __restrict__ dst) {
+  const int ox = blockIdx.x * blockDim.x + threadIdx.x;
+  const int oy = blockIdx.y;
+  const int b = blockIdx.z;
+  if (ox >= ow) return;
+  const int cn = CN ? CN : cn_rt;
+  const int y = oy - top, x = ox - left;
+  const bool inside = (unsigned)y < (unsigned)nh && (unsigned)x < (unsigned)nw;
+  ResizeTap cx{0, 0, 0, 0}, cy{0, 0, 0, 0};
+  if (inside && mode == RESIZE_LINEAR) {   // the taps from lb_tables_kernel
+    cx = ResizeTap{t.x0[x], t.x1[x], t.ca0[x], t.ca1[x]};
+    cy = ResizeTap{t.y0[y], t.y1[y], t.cb0[y], t.cb1[y]};
+  }
+  const size_t plane = (size_t)oh * ow;
+  lb_pixel_cn<OUT, CN>(inside, src + (size_t)b * H * W * cn, W, cn, mode, cx, cy, x, y, nw, pad, dst,
+                       ((size_t)b * oh + oy) * ow + ox, plane, (size_t)b * cn * plane + (size_t)oy * ow + ox);
+}
+
+template <int OUT, int CN>
+__global__ void letterbox_ragged_cn_kernel(LbChunk ch, int b0, int cn_rt, int oh, int ow, LbPad pad,
+                                           void* __restrict__ dst) {
+  const int ox = blockIdx.x * blockDim.x + threadIdx.x;
+  const int oy = blockIdx.y;
+  const LbFrame& f = ch.f[blockIdx.z];
+  const int b = b0 + blockIdx.z;
+  if (ox >= ow) return;
+  const int cn = CN ? CN : cn_rt;
+  const int y = oy - f.top, x = ox - f.left;
+  const bool inside = (unsigned)y < (unsigned)f.nh && (unsigned)x < (unsigned)f.nw;
+  ResizeTap cx{0, 0, 0, 0}, cy{0, 0, 0, 0};
+  if (inside && f.mode == RESIZE_LINEAR) {   // computed inline; the row pair is the same for a whole block
+    cx = resize_col_tap(x, f.sx, f.W);
+    cy = resize_row_tap(y, f.sy, f.H);
+  }
+  const size_t plane = (size_t)oh * ow;
+  lb_pixel_cn<OUT, CN>(inside, f.src, f.W, cn, f.mode, cx, cy, x, y, f.nw, pad, dst,
+                       ((size_t)b * oh + oy) * ow + ox, plane, (size_t)b * cn * plane + (size_t)oy * ow + ox);
+}
+
+template <int V>
+struct IntC {
+  static constexpr int value = V;
+};
+
+// call(out kind, channel count) with both as compile-time constants; counts above 4 share the run-time one
+template <class Call>
+void lb_dispatch_cn(int out_kind, int cn, Call call) {
+  const auto by_count = [&](auto out) {
+    switch (cn) {
+      case 1: call(out, IntC<1>{}); break;
+      case 2: call(out, IntC<2>{}); break;
+      case 3: call(out, IntC<3>{}); break;
+      case 4: call(out, IntC<4>{}); break;
+      default: call(out, IntC<0>{}); break;
+    }
+  };
+  if (out_kind == 0) by_count(IntC<0>{});
+  else if (out_kind == 1) by_count(IntC<1>{});
+  else by_count(IntC<2>{});
+}
+
+LbPad lb_pack_pad(const uint8_t* pad, int cn) {
+  LbPad p{0, 0};
+  for (int c = 0; c < cn; ++c) (c < 8 ? p.lo : p.hi) |= (uint64_t)pad[c] << ((c & 7) * 8);
+  return p;
+}
+
+LbChunk lb_chunk(const RaggedFrame* frames, int n) {
+  LbChunk ch;
+  for (int i = 0; i < RAGGED_CHUNK; ++i) {
+    const RaggedFrame& r = frames[std::min(i, n - 1)];   // unused records repeat the last one
+    LbFrame& f = ch.f[i];
+    f.src = r.src;
+    f.H = r.H; f.W = r.W; f.nh = r.nh; f.nw = r.nw; f.top = r.top; f.left = r.left;
+    f.sx = resize_scale(r.W, r.nw);
+    f.sy = resize_scale(r.H, r.nh);
+    f.mode = resize_mode(r.H, r.W, r.nh, r.nw);
+    f.reserved = 0;
+  }
+  return ch;
+}
+
 }  // namespace
+
+hipError_t launch_letterbox_ragged_cn(const RaggedFrame* frames, int B, int cn, int oh, int ow, const uint8_t* pad,
+                                      int swap_rb, int out_kind, void* dst, hipStream_t st) {
+  if (cn == 3) return launch_letterbox_ragged(frames, B, oh, ow, pad, swap_rb, out_kind, dst, st);
+  const LbPad p = lb_pack_pad(pad, cn);
+  for (int b0 = 0; b0 < B; b0 += RAGGED_CHUNK) {
+    const int n = std::min(RAGGED_CHUNK, B - b0);
+    const LbChunk ch = lb_chunk(frames + b0, n);
+    const dim3 grid((ow + 127) / 128, oh, n);
+    lb_dispatch_cn(out_kind, cn, [&](auto out, auto count) {
+      hipLaunchKernelGGL((letterbox_ragged_cn_kernel<decltype(out)::value, decltype(count)::value>), grid, dim3(128),
+                         0, st, ch, b0, cn, oh, ow, p, dst);
+    });
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
 
 hipError_t launch_letterbox_ragged(const RaggedFrame* frames, int B, int oh, int ow, const uint8_t pad[3],
                                    int swap_rb, int out_kind, void* dst, hipStream_t st) {
   for (int b0 = 0; b0 < B; b0 += RAGGED_CHUNK) {
     const int n = std::min(RAGGED_CHUNK, B - b0);
-    LbChunk ch;
-    for (int i = 0; i < RAGGED_CHUNK; ++i) {
-      const RaggedFrame& r = frames[b0 + std::min(i, n - 1)];   // unused records repeat the last one
-      LbFrame& f = ch.f[i];
-      f.src = r.src;
-      f.H = r.H; f.W = r.W; f.nh = r.nh; f.nw = r.nw; f.top = r.top; f.left = r.left;
-      f.sx = resize_scale(r.W, r.nw);
-      f.sy = resize_scale(r.H, r.nh);
-      f.mode = resize_mode(r.H, r.W, r.nh, r.nw);
-      f.reserved = 0;
-    }
+    const LbChunk ch = lb_chunk(frames + b0, n);
     const dim3 grid((ow + 127) / 128, oh, n);
     if (out_kind == 0)
       hipLaunchKernelGGL(letterbox_ragged_kernel<0>, grid, dim3(128), 0, st, ch, b0, oh, ow, pad[0], pad[1], pad[2],
@@ -200,6 +333,30 @@ hipError_t launch_letterbox(const uint8_t* src, int B, int H, int W, int nh, int
   else
     hipLaunchKernelGGL(letterbox_kernel<2>, grid, dim3(128), 0, st, src, H, W, nh, nw, top, left, oh, ow, pad[0],
                        pad[1], pad[2], mode, t, dst);
+  return hipGetLastError();
+}
+
+// Three channels written as launch_letterbox writes them (uint8, or float planes reversed) take its kernels.
+hipError_t launch_letterbox_cn(const uint8_t* src, int B, int H, int W, int cn, int nh, int nw, int top, int left,
+                               int oh, int ow, const uint8_t* pad, int swap_rb, int out_kind, void* dst, void* ws,
+                               hipStream_t st) {
+  if (cn == 3 && (out_kind == 0 || swap_rb))
+    return launch_letterbox(src, B, H, W, nh, nw, top, left, oh, ow, pad, out_kind, dst, ws, st);
+  int* w = reinterpret_cast<int*>(ws);
+  LbTab t{w, w + nw, w + 2 * nw, w + 3 * nw, w + 4 * nw, w + 4 * nw + nh, w + 4 * nw + 2 * nh, w + 4 * nw + 3 * nh};
+  const int mode = resize_mode(H, W, nh, nw);
+  if (mode == RESIZE_LINEAR) {
+    const int n = nw + nh;
+    hipLaunchKernelGGL(lb_tables_kernel, dim3((n + 255) / 256), dim3(256), 0, st, t, H, W, nh, nw);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  const LbPad p = lb_pack_pad(pad, cn);
+  const dim3 grid((ow + 127) / 128, oh, B);
+  lb_dispatch_cn(out_kind, cn, [&](auto out, auto count) {
+    hipLaunchKernelGGL((letterbox_cn_kernel<decltype(out)::value, decltype(count)::value>), grid, dim3(128), 0, st,
+                       src, H, W, cn, nh, nw, top, left, oh, ow, p, mode, t, dst);
+  });
   return hipGetLastError();
 }
 

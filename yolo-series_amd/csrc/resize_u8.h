@@ -62,6 +62,32 @@ __device__ __forceinline__ int resize_vertical(int d0, int d1, int b0, int b1, i
   return min(max(o, 0), 255);
 }
 
+// ---- cn interleaved channels (preprocess.hip's channel-count kernels).  The SIMD pass runs over the interleaved
+// destination row of nw * cn values, so the split is at resize_split(nw, cn) of pos = x * cn + c: neither the
+// 3-channel split nor a per-plane one (nw / 16 * 16) holds for another count.
+__host__ __device__ inline int resize_split(int nw, int cn) { return nw * cn / RESIZE_SIMD_LANES * RESIZE_SIMD_LANES; }
+
+__device__ __forceinline__ int resize_vertical_at(int d0, int d1, int b0, int b1, int pos, int nv) {
+  int o;
+  if (pos < nv) o = ((((d0 >> 4) * b0) >> 16) + (((d1 >> 4) * b1) >> 16) + 2) >> 2;
+  else o = (d0 * b0 + d1 * b1 + (1 << 21)) >> 22;
+  return min(max(o, 0), 255);
+}
+
+// channel c of destination pixel (x, y) of an H x W x cn packed source: one value, so a caller's channel loop
+// holds the fetches, the vertical pass and the store of one channel at a time.  The taps are the pixel's and are
+// read in the bilinear mode only.
+__device__ __forceinline__ int resize_value_cn(const uint8_t* __restrict__ img, int W, int cn, int mode,
+                                               const ResizeTap& cx, const ResizeTap& cy, int x, int y, int c, int nv) {
+  const auto fetch = [img, W, cn, c](int yy, int xx) -> int { return img[((size_t)yy * W + xx) * cn + c]; };
+  if (mode == RESIZE_IDENTITY) return fetch(y, x);
+  if (mode == RESIZE_AREA2X)
+    return (fetch(2 * y, 2 * x) + fetch(2 * y, 2 * x + 1) + fetch(2 * y + 1, 2 * x) + fetch(2 * y + 1, 2 * x + 1) + 2) >> 2;
+  const int d0 = fetch(cy.i0, cx.i0) * cx.c0 + fetch(cy.i0, cx.i1) * cx.c1;
+  const int d1 = fetch(cy.i1, cx.i0) * cx.c0 + fetch(cy.i1, cx.i1) * cx.c1;
+  return resize_vertical_at(d0, d1, cy.c0, cy.c1, x * cn + c, nv);
+}
+
 // destination pixel (x, y) of a bilinear resize with the taps cx, cy
 template <class Fetch>
 __device__ __forceinline__ void resize_linear_px(Fetch fetch, const ResizeTap& cx, const ResizeTap& cy, int x, int nw,

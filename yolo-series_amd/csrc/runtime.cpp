@@ -153,6 +153,65 @@ int yv7_letterbox_ragged(const yv7_frame_desc* frames, int B, int out_h, int out
   return 0;
 }
 
+static_assert(YV7_LETTERBOX_MAX_CH == yv7::LETTERBOX_MAX_CH, "the ABI's channel limit is the kernels'");
+
+// the checks the two channel-count entry points share; dst_align: the uint8 output's packed stores
+static int letterbox_c_args(const std::string& who, int channels, const uint8_t* pad, int swap_rb, int out_kind,
+                            const void* dst) {
+  if (channels < 1 || channels > YV7_LETTERBOX_MAX_CH)
+    return fail(YV7_E_ARG, who + ": channels must be 1.." + std::to_string(YV7_LETTERBOX_MAX_CH));
+  if (swap_rb && channels != 3) return fail(YV7_E_ARG, who + ": swap_rb needs channels == 3");
+  if (!pad) return fail(YV7_E_ARG, who + ": null pad");
+  if (out_kind < 0 || out_kind > 2) return fail(YV7_E_ARG, who + ": out_kind must be 0, 1 or 2");
+  if (out_kind == 0 && (channels == 2 || channels == 4) && reinterpret_cast<uintptr_t>(dst) % channels)
+    return fail(YV7_E_ARG, who + ": a uint8 dst of 2 / 4 channels must be aligned to one pixel");
+  return 0;
+}
+
+int yv7_letterbox_c(const void* src, int B, int H, int W, int channels, int new_h, int new_w, int top, int left,
+                    int out_h, int out_w, const uint8_t* pad, int swap_rb, int out_kind, void* dst, void* workspace,
+                    size_t ws_bytes, void* stream) {
+  if (!src || !dst || !workspace) return fail(YV7_E_ARG, "yv7_letterbox_c: null argument");
+  if (int rc = letterbox_c_args("yv7_letterbox_c", channels, pad, swap_rb, out_kind, dst)) return rc;
+  if (B <= 0 || H <= 0 || W <= 0 || new_h <= 0 || new_w <= 0 || top < 0 || left < 0 || top + new_h > out_h ||
+      left + new_w > out_w)
+    return fail(YV7_E_SHAPE, "yv7_letterbox_c: the resized image must lie inside the output canvas");
+  if (out_h > 65535 || B > 65535) return fail(YV7_E_SHAPE, "yv7_letterbox_c: at most 65535 rows and frames");
+  if ((size_t)B * H * W * channels >= ((size_t)1 << 40)) return fail(YV7_E_SHAPE, "yv7_letterbox_c: input too large");
+  if (ws_bytes < yv7::letterbox_workspace_bytes(new_h, new_w))
+    return fail(YV7_E_WORKSPACE, "yv7_letterbox_c: workspace too small");
+  hipError_t e = yv7::launch_letterbox_cn(reinterpret_cast<const uint8_t*>(src), B, H, W, channels, new_h, new_w, top,
+                                          left, out_h, out_w, pad, swap_rb != 0, out_kind, dst, workspace,
+                                          reinterpret_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return hip_fail(e, "yv7_letterbox_c launch");
+  return 0;
+}
+
+int yv7_letterbox_ragged_c(const yv7_frame_desc* frames, int B, int channels, int out_h, int out_w, const uint8_t* pad,
+                           int swap_rb, int out_kind, void* dst, void* workspace, size_t ws_bytes, void* stream) {
+  if (!frames || !dst) return fail(YV7_E_ARG, "yv7_letterbox_ragged_c: null argument");
+  if (B <= 0) return fail(YV7_E_ARG, "yv7_letterbox_ragged_c: B must be positive");
+  if (int rc = letterbox_c_args("yv7_letterbox_ragged_c", channels, pad, swap_rb, out_kind, dst)) return rc;
+  if (out_h <= 0 || out_w <= 0 || out_h > 65535)
+    return fail(YV7_E_SHAPE, "yv7_letterbox_ragged_c: canvas must be positive and at most 65535 rows");
+  for (int i = 0; i < B; ++i) {
+    const yv7_frame_desc& f = frames[i];
+    const std::string who = "yv7_letterbox_ragged_c: frame " + std::to_string(i);
+    if (!f.data) return fail(YV7_E_ARG, who + " has null data");
+    if (f.h <= 0 || f.w <= 0 || f.new_h <= 0 || f.new_w <= 0) return fail(YV7_E_SHAPE, who + " has a non-positive size");
+    if (f.top < 0 || f.left < 0 || (int64_t)f.top + f.new_h > out_h || (int64_t)f.left + f.new_w > out_w)
+      return fail(YV7_E_SHAPE, who + ": the resized image must lie inside the output canvas");
+    if ((size_t)f.h * f.w * channels >= ((size_t)1 << 40)) return fail(YV7_E_SHAPE, who + " is too large");
+  }
+  if (ws_bytes < yv7_letterbox_ragged_workspace_bytes(frames, B) || (ws_bytes > 0 && !workspace))
+    return fail(YV7_E_WORKSPACE, "yv7_letterbox_ragged_c: workspace null or too small");
+  hipError_t e = yv7::launch_letterbox_ragged_cn(reinterpret_cast<const yv7::RaggedFrame*>(frames), B, channels, out_h,
+                                                 out_w, pad, swap_rb != 0, out_kind, dst,
+                                                 reinterpret_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return hip_fail(e, "yv7_letterbox_ragged_c launch");
+  return 0;
+}
+
 int yv7_scale_boxes(float* det, const int32_t* count, int B, int max_det, const yv7_scale_desc* images,
                     int round_boxes, float* xywh, float* xyxyn, float* xywhn, void* stream) {
   if (!det || !count || !images) return fail(YV7_E_ARG, "yv7_scale_boxes: null argument");

@@ -354,6 +354,14 @@ struct ScaleImage {
 };
 hipError_t launch_letterbox_ragged(const RaggedFrame* frames, int B, int oh, int ow, const uint8_t pad[3],
                                    int swap_rb, int out_kind, void* dst, hipStream_t st);
+// cn interleaved channels, 1..LETTERBOX_MAX_CH, pad[cn] on the host; swap_rb with cn == 3 only.  cn == 3 runs the
+// kernels of the two launchers above wherever they write the same thing.
+constexpr int LETTERBOX_MAX_CH = 16;
+hipError_t launch_letterbox_cn(const uint8_t* src, int B, int H, int W, int cn, int nh, int nw, int top, int left,
+                               int oh, int ow, const uint8_t* pad, int swap_rb, int out_kind, void* dst, void* ws,
+                               hipStream_t st);
+hipError_t launch_letterbox_ragged_cn(const RaggedFrame* frames, int B, int cn, int oh, int ow, const uint8_t* pad,
+                                      int swap_rb, int out_kind, void* dst, hipStream_t st);
 // postprocess.hip
 hipError_t launch_scale_boxes(float* det, const int32_t* count, int B, int max_det, const ScaleImage* images,
                               int round_boxes, float* xywh, float* xyxyn, float* xywhn, hipStream_t st);

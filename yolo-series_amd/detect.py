@@ -28,11 +28,11 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from models.experimental import attempt_load  # noqa: E402
-from utils.datasets import (OUT_F16_CHW, OUT_F32_CHW, LoadImages, imread, letterbox_geometry,  # noqa: E402
-                            letterbox_ragged)
-from utils.general import (check_img_size, check_three_channels, nms_batched, non_max_suppression, scale_boxes, scale_coords,  # noqa: E402
+from utils.datasets import (FRAME_MODES, OUT_F16_CHW, OUT_F32_CHW, LoadImages, entry_channels,  # noqa: E402
+                            letterbox_geometry, letterbox_ragged, read_frame)
+from utils.general import (check_img_size, nms_batched, non_max_suppression, scale_boxes, scale_coords,  # noqa: E402
                            scale_desc, xyxy2xywh)
-from utils.plots import color_list, plot_boxes  # noqa: E402
+from utils.plots import color_list, display_frames, plot_boxes  # noqa: E402
 from utils.torch_utils import select_device, time_synchronized  # noqa: E402
 
 
@@ -41,15 +41,17 @@ def bgr_colors():
     return [c[::-1] for c in color_list()]
 
 
-def save_images(frames, paths, save_dir):
-    """Annotated BGR frames on the device -> save_dir / name, RGB, with PIL: one download for the group."""
+def save_images(frames, paths, save_dir, bgr=True):
+    """Annotated frames on the device (BGR, or display copies in RGB order) -> save_dir / name, RGB, with PIL: one
+    download for the group."""
     from PIL import Image
     flat = torch.cat([f.reshape(-1) for f in frames]).cpu().numpy()
     off = 0
     for f, path in zip(frames, paths):
         im = flat[off:off + f.numel()].reshape(tuple(f.shape))
         off += f.numel()
-        Image.fromarray(im[:, :, ::-1]).save(save_dir / Path(path).name)
+        Image.fromarray(im[:, :, ::-1] if bgr else im).save(save_dir / Path(path).with_suffix(
+            '.png' if Path(path).suffix.lower() == '.npy' else Path(path).suffix).name)
 
 
 def load_model(opt, device):
@@ -62,21 +64,31 @@ def load_model(opt, device):
     return attempt_load(m, map_location=device)
 
 
+def draw(im0s, det, cnt, names, bgr, device):
+    """detect.py:216-218: name + conf, thickness 1, the last row first.  BGR frames are drawn in place; frames of
+    a stated mode (--frames) on their 3-channel display copies, which are in RGB order."""
+    if bgr:
+        return plot_boxes(im0s, det, cnt, names=names, colors=bgr_colors(), line_thickness=1, reverse=True)
+    return plot_boxes(display_frames(im0s, device), det, cnt, names=names, colors=color_list(), line_thickness=1,
+                      reverse=True)
+
+
 def detect_batched(opt, model, dataset, imgsz, half, names, save_dir):
     """The loop of detect() over groups of up to opt.batch_size files, each group one forward."""
     device = next(model.parameters()).device
+    bgr = dataset.frames in (None, 'RGB')
     results = []
     files = dataset.files
     for g0 in range(0, len(files), opt.batch_size):
         paths = files[g0:g0 + opt.batch_size]
-        im0s = [imread(p) for p in paths]                  # BGR, sizes may differ
+        im0s = [read_frame(p, dataset.frames, dataset.channels) for p in paths]   # BGR / frame order, sizes differ
         geoms = [letterbox_geometry(im0.shape[:2], (imgsz, imgsz), auto=False) for im0 in im0s]   # datasets.py:196
         if opt.save_img:   # one upload: the letterbox and the drawing take the same tensors
             packed = torch.from_numpy(np.concatenate([im0.reshape(-1) for im0 in im0s])).to(device)
             sizes = [im0.size for im0 in im0s]
             im0s = [p.view(im0.shape) for p, im0 in zip(packed.split(sizes), im0s)]
         t1 = time_synchronized()
-        img = letterbox_ragged(im0s, geoms, (imgsz, imgsz), swap_rb=True, device=device,
+        img = letterbox_ragged(im0s, geoms, (imgsz, imgsz), swap_rb=bgr, device=device,
                                out_kind=OUT_F16_CHW if half else OUT_F32_CHW)
         with torch.no_grad():
             pred = model(img, augment=opt.augment)[0]
@@ -85,9 +97,8 @@ def detect_batched(opt, model, dataset, imgsz, half, names, save_dir):
         scale_boxes(det, cnt, [scale_desc(img.shape[2:], im0.shape) for im0 in im0s], round_boxes=True, views=False)
         counts = cnt.tolist()
         t3 = time_synchronized()
-        if opt.save_img:   # detect.py:216-218: name + conf, thickness 1, the last row first
-            save_images(plot_boxes(im0s, det, cnt, names=names, colors=bgr_colors(), line_thickness=1, reverse=True),
-                        paths, save_dir)
+        if opt.save_img:
+            save_images(draw(im0s, det, cnt, names, bgr, device), paths, save_dir, bgr)
         for i, (path, im0) in enumerate(zip(paths, im0s)):
             d, s = det[i, :counts[i]].cpu(), ''
             gn = torch.tensor(im0.shape)[[1, 0, 1, 0]]      # normalization gain whwh
@@ -114,14 +125,16 @@ def detect(opt):
         raise RuntimeError('detect.py: the MI355X path has no CPU execution (oracle/ holds the CPU reference)')
     half = not opt.fp32                                   # detect.py:38 (half on every GPU device)
     model = load_model(opt, device)
-    check_three_channels(model)
+    frames = getattr(opt, 'frames', None)
+    ch = entry_channels(model, frames)
+    bgr = frames in (None, 'RGB')
     stride = int(model.stride.max())
     imgsz = check_img_size(opt.img_size, s=stride)
     if half:
         model.half()
-    dataset = LoadImages(opt.source, img_size=imgsz, stride=stride)
+    dataset = LoadImages(opt.source, img_size=imgsz, stride=stride, frames=frames, channels=ch)
     names = model.module.names if hasattr(model, 'module') else model.names
-    model(torch.zeros(1, 3, imgsz, imgsz).to(device).type_as(next(model.parameters())))  # run once
+    model(torch.zeros(1, ch, imgsz, imgsz).to(device).type_as(next(model.parameters())))  # run once
     save_dir = Path(opt.project) / opt.name
     if opt.save_txt:
         (save_dir / 'labels').mkdir(parents=True, exist_ok=True)
@@ -163,8 +176,7 @@ def detect(opt):
             if opt.save_img:   # detect.py:216-218 through the batch's drawing path, a batch of one
                 cnt = torch.tensor([len(det)], dtype=torch.int32, device=device)
                 box = det[None].float().contiguous() if len(det) else torch.zeros((1, 1, 6), device=device)
-                save_images(plot_boxes([im0], box, cnt, names=names, colors=bgr_colors(), line_thickness=1,
-                                       reverse=True), [path], save_dir)
+                save_images(draw([im0], box, cnt, names, bgr, device), [path], save_dir, bgr)
             if not opt.quiet:
                 print(f'{s}Done. ({(1E3 * (t2 - t1)):.1f}ms) Inference, ({(1E3 * (t3 - t2)):.1f}ms) NMS')
             results.append((path, det.cpu()))
@@ -194,6 +206,8 @@ def parse_opt(argv=None):
     ap.add_argument('--name', default='exp', help='save results to project/name')
     ap.add_argument('--fp32', action='store_true', help='run the fp32 plan instead of half()')
     ap.add_argument('--batch-size', type=int, default=1, help='files per forward (sizes may differ); 1 = one by one')
+    ap.add_argument('--frames', choices=FRAME_MODES, default=None, help='how files become the frames of a model of '
+                    'another channel count: a PIL mode, or raw for the file\'s own 8-bit bands / .npy arrays')
     ap.add_argument('--quiet', action='store_true')
     return ap.parse_args(argv)
 

@@ -26,9 +26,9 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from utils.datasets import OUT_F16_CHW, OUT_F32_CHW, autoshape_geometry, letterbox_ragged
-from utils.general import check_three_channels, increment_path, nms_batched, non_max_suppression, scale_boxes, xyxy2xywh
-from utils.plots import color_list, plot_boxes
+from utils.datasets import OUT_F16_CHW, OUT_F32_CHW, autoshape_geometry, entry_channels, imread, letterbox_ragged
+from utils.general import increment_path, nms_batched, non_max_suppression, scale_boxes, xyxy2xywh
+from utils.plots import color_list, display_frames, plot_boxes
 from utils.torch_utils import fuse_conv_and_bn, time_synchronized
 
 
@@ -243,16 +243,41 @@ def _as_hwc3(im):
     return im[:, :, :3] if im.ndim == 3 else np.tile(im[:, :, None], 3)
 
 
+def _as_hwc(im, C):
+    """One decoded image as the uint8 [H, W, C] frame of a C-channel model (autoShape with a frame mode): [H, W]
+    becomes [H, W, 1] for C = 1, [C, H, W] is transposed when only its first axis can be the channels; nothing is
+    dropped or tiled, so any other channel count is an error."""
+    is_t = isinstance(im, torch.Tensor)
+    if not ((isinstance(im, np.ndarray) and im.dtype == np.uint8) or (is_t and im.dtype == torch.uint8)):
+        raise ValueError(f'autoShape: images must be uint8 (got {getattr(im, "dtype", type(im).__name__)}); '
+                         f'scale and convert before the call')
+    if is_t and not im.is_cuda:
+        raise ValueError(f'autoShape: a tensor image must be on the HIP device, got {im.device}')
+    shape = tuple(im.shape)
+    if im.ndim == 2 and C == 1:
+        im = im[:, :, None]
+    if im.ndim == 3 and im.shape[0] == C != im.shape[2]:
+        im = im.permute(1, 2, 0) if is_t else im.transpose((1, 2, 0))
+    if im.ndim != 3 or im.shape[2] != C:
+        raise ValueError(f'autoShape: expected an image of {C} channels (HWC or CHW), got shape {shape}')
+    return im
+
+
 class autoShape(nn.Module):  # common.py:865-932
     """Input-robust model wrapper: filenames, PIL images, uint8 numpy arrays (HWC / CHW / HW) or uint8 HWC HIP
-    tensors, one or a list, any sizes, RGB -> Detections.  A float tensor goes straight to the model."""
+    tensors, one or a list, any sizes, RGB -> Detections.  A float tensor goes straight to the model.
+    frames (utils.datasets.FRAME_MODES) states how files and images become the frames of a model of another
+    channel count: files through imread(path, frames), PIL images converted to that mode (taken as they are for
+    'raw'), arrays and HIP tensors as [H, W, C] / [C, H, W] of exactly the model's channels, in their own order.
+    With frames=None a model of another count is refused, as ever."""
     conf = 0.25     # NMS confidence threshold
     iou = 0.45      # NMS IoU threshold
     classes = None  # (optional list) filter by class
 
-    def __init__(self, model):
+    def __init__(self, model, frames=None):
         super().__init__()
-        check_three_channels(model)
+        self.ch = entry_channels(model, frames)
+        self.frames = frames
         self.model = model.eval()
 
     def autoshape(self):
@@ -272,6 +297,15 @@ class autoShape(nn.Module):  # common.py:865-932
         files = []
         for i, im in enumerate(imgs):
             f = f'image{i}'
+            if self.frames is not None:
+                if isinstance(im, (str, Path)):
+                    im, f = imread(im, self.frames), str(im)
+                elif hasattr(im, 'convert') and hasattr(im, 'size'):   # PIL Image
+                    f = getattr(im, 'filename', f) or f
+                    im = np.asarray(im if self.frames == 'raw' else im.convert(self.frames))
+                files.append(Path(f).with_suffix('.jpg').name)
+                imgs[i] = _as_hwc(im, self.ch)
+                continue
             if isinstance(im, (str, Path)):
                 from PIL import Image
                 if str(im).startswith('http'):
@@ -350,14 +384,19 @@ class Detections:  # common.py:935-1012
             det = torch.zeros((self.n, max(int(cnt.max()), 1), 6), dtype=torch.float32, device=dev)
             for i, p in enumerate(self.pred):
                 det[i, :len(p)] = p
-        out = plot_boxes(self.imgs, det, cnt, names=self.names, colors=color_list(), reverse=False)
+        frames = self.imgs
+        if any(im.shape[2] != 3 for im in frames):   # the drawing is 3-channel: draw on display copies
+            frames = display_frames(frames, det.device)
+        out = plot_boxes(frames, det, cnt, names=self.names, colors=color_list(), reverse=False)
         host = [i for i, im in enumerate(self.imgs) if isinstance(im, np.ndarray)]
+        for i, im in enumerate(self.imgs):
+            if isinstance(im, torch.Tensor):
+                self.imgs[i] = out[i]
         if host:   # one download for the batch
             flat = torch.cat([out[i].reshape(-1) for i in host]).cpu().numpy()
             off = 0
             for i in host:
-                shape = self.imgs[i].shape
-                self.imgs[i] = flat[off:off + out[i].numel()].reshape(shape)
+                self.imgs[i] = flat[off:off + out[i].numel()].reshape(tuple(out[i].shape))
                 off += out[i].numel()
 
     def show(self):

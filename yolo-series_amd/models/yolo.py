@@ -297,9 +297,9 @@ class Model(nn.Module):
         self.info()
         return self
 
-    def autoshape(self):  # yolo.py:726-730
+    def autoshape(self, frames=None):  # yolo.py:726-730; frames: see autoShape
         print('Adding autoShape... ')
-        m = autoShape(self)   # wrap model
+        m = autoShape(self, frames)   # wrap model
         for k in ('yaml', 'nc', 'hyp', 'names', 'stride'):   # copy_attr(include=...): the attributes that exist
             if k in self.__dict__:
                 setattr(m, k, self.__dict__[k])

@@ -49,11 +49,11 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from models.experimental import attempt_load  # noqa: E402
-from utils.datasets import ValLoader, create_dataloader  # noqa: E402
-from utils.general import (check_dataset, check_file, check_img_size, check_three_channels, coco80_to_coco91_class,  # noqa: E402
+from utils.datasets import FRAME_MODES, ValLoader, create_dataloader, entry_channels  # noqa: E402
+from utils.general import (check_dataset, check_file, check_img_size, coco80_to_coco91_class,  # noqa: E402
                            increment_path, nms_batched, scale_boxes, xyxy2xywh)
 from utils.metrics import ConfusionMatrix, ap_per_class, match_batch  # noqa: E402
-from utils.plots import mosaic_tables, plot_images  # noqa: E402
+from utils.plots import display_copy, mosaic_tables, plot_images  # noqa: E402
 from utils.torch_utils import select_device  # noqa: E402
 
 # what the reference reads from its global `opt` when called directly (test.py:51, 54, 90); the CLI replaces it
@@ -128,7 +128,8 @@ def test(data,
          half_precision=True,
          trace=False,
          is_coco=False,
-         v5_metric=False):
+         v5_metric=False,
+         frames=None):
     if save_hybrid:
         raise NotImplementedError('save_hybrid (autolabelling through NMS labels=) is not part of the MI355X path')
     if compute_loss is not None:
@@ -146,7 +147,7 @@ def test(data,
         save_dir = Path(increment_path(Path(opt.project) / opt.name, exist_ok=opt.exist_ok))
         (save_dir / 'labels' if save_txt else save_dir).mkdir(parents=True, exist_ok=True)
         model = load_model(weights, device)
-        check_three_channels(model)   # (the loader below is this function's own)
+        ch = entry_channels(model, frames)   # (the loader below is this function's own)
         gs = max(int(model.stride.max()), 32)
         imgsz = check_img_size(imgsz, s=gs)
     elif save_txt:
@@ -169,10 +170,11 @@ def test(data,
     niou = iouv.numel()
 
     if not training:
-        model(torch.zeros(1, 3, imgsz, imgsz).to(device).type_as(next(model.parameters())))  # run once
+        model(torch.zeros(1, ch, imgsz, imgsz).to(device).type_as(next(model.parameters())))  # run once
         task = opt.task if opt.task in ('train', 'val', 'test') else 'val'
         dataloader = create_dataloader('Test', data[task], imgsz, batch_size, gs, opt, pad=0.5, rect=True,
-                                       prefix=f'{task}: ', data_dict=data, half=half, device=device)[0]
+                                       prefix=f'{task}: ', data_dict=data, half=half, device=device, frames=frames,
+                                       channels=ch)[0]
     if v5_metric:
         print('Testing with YOLOv5 AP metric...')
 
@@ -207,6 +209,8 @@ def test(data,
         """Batch k onto the stream; returns its slot.  Nothing here waits for the device."""
         img = img.to(device, non_blocking=True)
         img_plot = img   # the uint8 batch where the loader supplied one
+        if write_plots and k < 3 and img.shape[1] != 3:
+            img_plot = display_copy(img, 1)   # the picture grid is 3-channel
         if not img.is_floating_point():
             img = (img.half() if half else img.float()) / 255.0   # uint8 to fp16/32, 0 - 255 to 0.0 - 1.0
         elif img.dtype != dtype:
@@ -400,6 +404,8 @@ def parse_opt(argv=None):
     parser.add_argument('--name', default='exp', help='save to project/name')
     parser.add_argument('--exist-ok', action='store_true', help='existing project/name ok, do not increment')
     parser.add_argument('--no-trace', action='store_true', help='accepted and ignored: nothing is traced here')
+    parser.add_argument('--frames', choices=FRAME_MODES, default=None, help='how files become the frames of a model '
+                        'of another channel count: a PIL mode, or raw for 8-bit bands / .npy arrays')
     parser.add_argument('--v5-metric', action='store_true', help='assume maximum recall as 1.0 in AP calculation')
     o = parser.parse_args(argv)
     o.save_json |= o.data.endswith('coco.yaml')
@@ -415,10 +421,10 @@ def main(argv=None):
         return test(opt.data, opt.weights, opt.batch_size, opt.img_size, opt.conf_thres, opt.iou_thres,
                     opt.save_json, opt.single_cls, opt.augment, opt.verbose, save_txt=opt.save_txt | opt.save_hybrid,
                     save_hybrid=opt.save_hybrid, save_conf=opt.save_conf, trace=not opt.no_trace,
-                    v5_metric=opt.v5_metric)
+                    v5_metric=opt.v5_metric, frames=opt.frames)
     if opt.task == 'speed':   # speed benchmarks
         return [test(opt.data, w, opt.batch_size, opt.img_size, 0.25, 0.45, save_json=False, plots=False,
-                     v5_metric=opt.v5_metric) for w in (opt.weights or [None])]
+                     v5_metric=opt.v5_metric, frames=opt.frames) for w in (opt.weights or [None])]
     raise NotImplementedError(f'--task {opt.task}: only val, test and speed are part of the MI355X path')
 
 

@@ -44,6 +44,14 @@ def check_three_channels(model):
             raise RuntimeError('this entry point loads 3-channel images; call the model on a [B,C,H,W] tensor')
 
 
+def input_channels(model):
+    """The input channel count of a model, or the one all members of an Ensemble share."""
+    chs = {getattr(m, 'yaml', {}).get('ch', 3) for m in (model if isinstance(model, torch.nn.ModuleList) else [model])}
+    if len(chs) != 1:
+        raise ValueError(f'the ensemble mixes input channel counts {sorted(chs)}')
+    return chs.pop()
+
+
 def check_file(file):  # general.py:146-154
     if file == '' or Path(file).is_file():
         return file

@@ -38,6 +38,32 @@ def line_thickness(shape):   # plots.py:59: line / font thickness of an image of
 _line_thickness = line_thickness   # plot_boxes has a parameter of that name
 
 
+def display_channels(C):
+    """Which channels of a C-channel frame a 3-channel picture of it shows: the first three, a pair as (0, 1, 1),
+    a single band three times.  The drawing and mosaic kernels stay 3-channel and take such copies."""
+    return (0, 1, 2) if C >= 3 else (0, 1, 1) if C == 2 else (0, 0, 0)
+
+
+def display_copy(x, dim):
+    """The 3-channel display copy of a device tensor whose channels lie along `dim` ([H, W, C] frames: 2,
+    [B, C, H, W] batches: 1), contiguous.  Slices and one cat: nothing here waits for the device."""
+    return torch.cat([x.narrow(dim, c, 1) for c in display_channels(x.shape[dim])], dim).contiguous()
+
+
+def display_frames(frames, device):
+    """display_copy of each uint8 [H, W, C] frame (numpy arrays travel in one packed upload, HIP tensors are read in
+    place and left as they are) -> a list of [H, W, 3] HIP tensors plot_boxes may draw on."""
+    ptrs, keep = pack_frames(frames, device)
+    packed = keep[0] if any(isinstance(f, np.ndarray) for f in frames) else None
+    out = []
+    for f, p in zip(frames, ptrs):
+        if isinstance(f, np.ndarray):
+            o = p - packed.data_ptr()
+            f = packed[o:o + f.size].view(f.shape)
+        out.append(display_copy(f, 2))
+    return out
+
+
 def text_height(t):
     """The glyph cell's height for line thickness t.  The reference draws cv2's 22-pixel face at fontScale t / 3;
     22 pixels is that face's height above the baseline, and the cell here also holds the descenders, which in PIL's

@@ -125,6 +125,10 @@ SIGNATURES = {
     'yv7_letterbox': (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     'yv7_letterbox_ragged_workspace_bytes': (_sz, [ctypes.POINTER(FrameDesc), _i]),
     'yv7_letterbox_ragged': (_i, [ctypes.POINTER(FrameDesc), _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    'yv7_letterbox_c': (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_uint8), _i, _i, _vp, _vp,
+                             _sz, _vp]),
+    'yv7_letterbox_ragged_c': (_i, [ctypes.POINTER(FrameDesc), _i, _i, _i, _i, ctypes.POINTER(ctypes.c_uint8), _i, _i,
+                                    _vp, _vp, _sz, _vp]),
     'yv7_scale_boxes': (_i, [_vp, _vp, _i, _i, ctypes.POINTER(ScaleDesc), _i, _vp, _vp, _vp, _vp]),
     'yv7_match': (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, ctypes.POINTER(ScaleDesc), _i, _i, ctypes.POINTER(_f), _i,
                        _vp, _vp, _vp]),
